@@ -17,7 +17,19 @@ Workload
           (weak scaling: the same loci per GPU as N = 1).  --wgs splits the whole 3.1 G-locus
           genome instead (configs[3]: ~390 M loci per GPU at N = 8).
 
-Also reported:
+A plain run sets up (reads generated and uploaded, one untimed first call), warms up, times the
+steps, writes the last timed step's records with --dump-outputs DIR and prints the result line.
+
+--dump-outputs DIR
+  the records the last timed step left (the result image a caller of the step receives, copied
+  to the host after the timed bracket): DIR/<field>.npy for each record array (contig, pos,
+  sample, gt0, gt1, flags, ref_off, ref_len, alt_off, alt_len; float64), DIR/allele_pool.npy
+  (the allele bytes, float32) and DIR/counters.npy (records, visited, complex, ambiguous and
+  tie loci; float64).  Past 64 MB a fixed seeded sample of the records (DIR/sample_index.npy)
+  and the head of the pool are written.  The inputs are seeded: the same arguments give the
+  same reads.  At N > 1 each rank writes its own records as DIR/rank<k>_<field>.npy.
+
+--full adds (each a run of its own, after the timed steps):
   roofline      germline_proj's algorithmic bytes / its HIP-event time vs 8 TB/s
   end_to_end    SoA upload (H2D + upload-time derivation), the step, the results' D2H, and
                 BAM ingest (native libgqingest, rate measured on a sample BAM) for the shard
@@ -114,7 +126,16 @@ def main() -> int:
                          "multi-GPU ingest path, on this GPU)")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_r06.json"),
                     help="PMC-derived HBM bytes per pileup launch (from a separate rocprofv3 --pmc pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure: "
+                         "per-stage and roofline figures, the resident and host-copy steps, ingest, the CLI single "
+                         "pass, the CPU baseline and parity windows, somatic, configs[4] and the configs[3] rank "
+                         "share (the --no-* / --*-length options choose among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the records of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N: one rank per GPU.  Without a launcher (WORLD_SIZE unset) N > 1 starts the N ranks
     # itself as a child torch.distributed.run job, before anything here touches the GPU.
@@ -207,7 +228,7 @@ def main() -> int:
     first = step(resident=True)
     cold_ms = (time.perf_counter() - t) * 1e3
     cold_tm = ctx.timings()
-    first_rows = first.to_host().tuples(g.contig_names) if rank == 0 and world == 1 else None
+    first_rows = first.to_host().tuples(g.contig_names) if args.full and rank == 0 and world == 1 else None
     for _ in range(args.warmup):
         step()
     barrier()
@@ -222,7 +243,9 @@ def main() -> int:
         step_ms.append((time.perf_counter() - t1) * 1e3)
     barrier()
     elapsed = time.perf_counter() - t
-    for _ in range(args.steps):  # the same steps again, untimed, for the per-stage figures
+    if args.dump_outputs:  # (before the next germline call on the context reuses the result image)
+        dump_outputs(args.dump_outputs, calls.to_host(), "rank%d_" % rank if world > 1 else "")
+    for _ in range(args.steps if args.full else 0):  # the same steps again, untimed, for the per-stage figures
         calls = step()
         sync()
         tm = ctx.timings()
@@ -241,7 +264,7 @@ def main() -> int:
     # the re-derived pass gives the records of the first call on the freshly uploaded set
     rederive_identical = None if first_rows is None else calls.to_host().tuples(g.contig_names) == first_rows
     res_ms = []
-    for _ in range(max(5, min(args.steps, 20))):
+    for _ in range(max(5, min(args.steps, 20)) if args.full else 0):
         t1 = time.perf_counter()
         calls = step(resident=True)
         sync()
@@ -261,6 +284,39 @@ def main() -> int:
     visited = int(calls.visited_loci)
     if args.calls_out:  # (before the next germline call on the context reuses the result image)
         write_calls(args, calls, g, gather_dev, world, rank)
+    n_reads = int(g.arrays["start"].shape[0])
+    line = {
+        "metric": "pileup loci/sec at 30x WGS; achieved HBM GB/s vs roofline",
+        "value": loci_total * args.steps / elapsed,
+        "unit": "loci/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (native generator: 30x, L=150, GC 0.41, het/hom SNV + indels + Phred errors)",
+        "config": {"workload": workload, "genome_loci": genome_loci, "visited_loci_per_gpu": visited,
+                   "reads_per_gpu": n_reads, "contigs_per_gpu": len(g.contig_names), "depth": args.depth,
+                   "read_len": 150, "threshold": args.threshold, "parallelism": "loci-sharded x%d" % world},
+        "step_ms_median": float(np.median(step_ms)),
+        "calls": len(calls),
+        "complex_loci": int(calls.complex_loci),
+        "ambiguous_loci": int(calls.ambiguous_loci),
+        # loci with a count tie among passing alleles (their order is the restated Scala map
+        # order), and loci whose order also depends on first occurrences (redone in element order)
+        "tie_loci": int(calls.tie_loci),
+        "order_loci": int(ctx.timings()["order_loci"]),
+        "gen_s": gen_s,
+    }
+    if not args.full:  # a plain run ends here: the headline figure and the run's own counters
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(line))
+        return 0
     # the same pass with the records copied to the host (PCIe-inclusive), a few steps, rank-local
     hc = ctx.germline_threshold(reads, loci, args.threshold)  # warm-up of the host-block path
     n_host = 5
@@ -278,7 +334,6 @@ def main() -> int:
     #      projection rows of 4-bit codes, 8-B sparse entries).
     st = ctx.proj_stats(reads)
     a = g.arrays
-    n_reads = int(a["start"].shape[0])
     bytes_seq = int(a["seq"].shape[0])
     bytes_meta = 16 * n_reads
     bytes_cigar = 4 * int(a["cigar"].shape[0])
@@ -332,22 +387,7 @@ def main() -> int:
                          "written (%d B); kernel_ms: median of the steps' HIP-event times on the context's "
                          "stream" % (elements, int(st["proj_bytes"]))}
 
-    line = {
-        "metric": "pileup loci/sec at 30x WGS; achieved HBM GB/s vs roofline",
-        "value": loci_total * args.steps / elapsed,
-        "unit": "loci/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (native generator: 30x, L=150, GC 0.41, het/hom SNV + indels + Phred errors)",
-        "config": {"workload": workload, "genome_loci": genome_loci, "visited_loci_per_gpu": visited,
-                   "reads_per_gpu": n_reads, "contigs_per_gpu": len(g.contig_names), "depth": args.depth,
-                   "read_len": 150, "threshold": args.threshold, "parallelism": "loci-sharded x%d" % world},
+    line.update({
         "roofline": roof,
         # the resident call's pileup kernel (the round-4 headline kernel)
         "call_roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -375,15 +415,7 @@ def main() -> int:
         "device_stages_ms": {k: float(np.mean(v)) for k, v in stage_ms.items()},
         "host_results_loci_per_s": visited / (host_ms_step * 1e-3),
         "host_results_ms_per_step": host_ms_step,
-        "calls": len(calls),
-        "complex_loci": int(calls.complex_loci),
-        "ambiguous_loci": int(calls.ambiguous_loci),
-        # loci with a count tie among passing alleles (their order is the restated Scala map
-        # order), and loci whose order also depends on first occurrences (redone in element order)
-        "tie_loci": int(calls.tie_loci),
-        "order_loci": int(ctx.timings()["order_loci"]),
-        "gen_s": gen_s,
-    }
+    })
     # one shot: a cold device call on resident reads = the upload-time derivation + the first
     # call (which derives the projection: slice windows, rows, 4-bit codes, sparse entries)
     one = float(st_upload["derive_ms"]) + cold_ms
@@ -439,6 +471,35 @@ def launch_ranks(n: int) -> int:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd).returncode
+
+
+DUMP_BUDGET = 64_000_000  # bytes over all the files of one --dump-outputs
+
+
+def dump_outputs(path: str, calls, prefix: str = ""):
+    """The step's records (a GermlineCalls: the result image copied to the host) as
+    <path>/<prefix><name>.npy: the record arrays and the counters in float64 (positions and pool
+    offsets are below 2^53: exact), the allele pool's bytes in float32.  Within DUMP_BUDGET bytes
+    in all: past it, the records at a fixed seeded sample of indices (sample_index.npy, ascending)
+    and the head of the pool."""
+    os.makedirs(path, exist_ok=True)
+    names = ("contig", "pos", "sample", "gt0", "gt1", "flags", "ref_off", "ref_len", "alt_off", "alt_len")
+    n = len(calls)
+    pool = np.frombuffer(calls.pool, np.uint8)
+    out = {"counters": np.array([n, calls.visited_loci, calls.complex_loci, calls.ambiguous_loci, calls.tie_loci],
+                                np.float64)}
+    half = DUMP_BUDGET // 2 - 4096  # records and pool: half each, .npy headers allowed for
+    keep = half // (8 * (len(names) + 1))
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20261015).choice(n, size=keep, replace=False))
+        out["sample_index"] = idx.astype(np.float64)
+    for k in names:
+        col = np.asarray(calls.a[k])
+        out[k] = (col if idx is None else col[idx]).astype(np.float64)
+    out["allele_pool"] = pool[:half // 4].astype(np.float32)
+    for k, v in out.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v)
 
 
 def write_calls(args, calls, g, gather_dev, world: int, rank: int):

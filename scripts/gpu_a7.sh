@@ -2,16 +2,17 @@
 # round-4 step: GPU tests, the somatic caller A/B (waves per SIMD) with phase clocks, a HIP API
 # trace of the germline bench (derivation's host-side costs), then the bench line.
 TAG=$1
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 stop() { case $1 in 124|134|137|139) echo "step rc=$1: stopping"; exit $1;; esac; }
-timeout -k 10 700 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > gpurun_out/${TAG}_tests.log 2>&1
+timeout -k 10 700 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > $OUT/${TAG}_tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; stop $rc
-GQ_DBG=16 timeout -k 10 300 python -u scripts/bench_somatic.py --steps 3 --warmup 1 --cpu-window 0 > gpurun_out/${TAG}_som_wpe3.txt 2>&1
+GQ_DBG=16 timeout -k 10 300 python -u scripts/bench_somatic.py --steps 3 --warmup 1 --cpu-window 0 > $OUT/${TAG}_som_wpe3.txt 2>&1
 rc=$?; echo "som3 rc=$rc"; stop $rc
-GQ_CALL_WPE=2 GQ_DBG=16 timeout -k 10 300 python -u scripts/bench_somatic.py --steps 3 --warmup 1 --cpu-window 0 > gpurun_out/${TAG}_som_wpe2.txt 2>&1
+GQ_CALL_WPE=2 GQ_DBG=16 timeout -k 10 300 python -u scripts/bench_somatic.py --steps 3 --warmup 1 --cpu-window 0 > $OUT/${TAG}_som_wpe2.txt 2>&1
 rc=$?; echo "som2 rc=$rc"; stop $rc
-timeout -k 10 300 rocprofv3 --hip-trace --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_hip -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass > gpurun_out/${TAG}_hip.log 2>&1
+timeout -k 10 300 rocprofv3 --hip-trace --kernel-trace --stats --output-format csv -d $OUT/${TAG}_hip -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass > $OUT/${TAG}_hip.log 2>&1
 rc=$?; echo "hiptrace rc=$rc"; stop $rc
-timeout -k 10 400 python -u bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+timeout -k 10 400 python -u bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 rc=$?; echo "bench rc=$rc"; exit $rc

@@ -9,7 +9,7 @@ if [ $# -gt 0 ]; then
   timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu "$@" > gpurun_out/${TAG}_tests.log 2>&1
   rc=$?; echo "tests rc=$rc"; tail -3 gpurun_out/${TAG}_tests.log; stop $rc
 fi
-B="--steps 10 --warmup 3 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline --no-configs3 ${BENCH_ARGS}"
+B="--full --steps 10 --warmup 3 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline --no-configs3 ${BENCH_ARGS}"
 timeout -k 10 300 python -u bench.py $B > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
 rc=$?; echo "bench rc=$rc"; stop $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof -o run -- python3 bench.py $B > gpurun_out/${TAG}_prof.log 2>&1

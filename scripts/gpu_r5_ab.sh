@@ -4,7 +4,7 @@
 TAG=$1; KRE=$2; shift 2
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="--steps 5 --warmup 1 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline --no-configs3 ${BENCH_ARGS}"
+B="--full --steps 5 --warmup 1 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline --no-configs3 ${BENCH_ARGS}"
 i=0
 for v in "$@"; do
   i=$((i+1))

@@ -3,7 +3,7 @@
 TAG=$1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="--length 1000000 --steps 3 --warmup 1 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline"
+B="--full --length 1000000 --steps 3 --warmup 1 --somatic-length 0 --panel-length 0 --no-single-pass --no-cpu-baseline"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof -o run -- python3 bench.py $B > gpurun_out/${TAG}_prof.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -ne 0 ] && exit $rc
 f=$(find gpurun_out/${TAG}_prof -name run_kernel_stats.csv | head -1)

@@ -5,7 +5,7 @@
 OUT=$1; KRE=$2
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--steps 2 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3"
+B="--full --steps 2 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3"
 i=0
 for G in "TA_TA_BUSY TA_ADDR_STALLED_BY_TC_CYCLES TD_TD_BUSY TD_TC_STALL GRBM_GUI_ACTIVE SQ_WAVES SQ_INST_LEVEL_VMEM SQ_WAVE_CYCLES" \
          "TCP_TCC_READ_REQ_LATENCY TCP_TCC_READ_REQ TCP_PENDING_STALL_CYCLES TCP_UTCL1_TRANSLATION_MISS SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" \

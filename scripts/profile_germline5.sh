@@ -6,7 +6,7 @@ OUT=$1
 KRE=${KRE:-"proj_fill_cells|germline_proj|row_count|read_prep|pev_fill|pool_clean|col_derive|proj_prep"}
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3"
+B="--full --steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3"
 run() { "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step rc=$rc: $*"; exit $rc; fi; }
 run timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $B > $OUT/trace.log 2>&1
 i=0

@@ -5,7 +5,7 @@
 OUT=$1
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3 ${BENCH_ARGS}"
+B="--full --steps 3 --warmup 1 --no-cpu-baseline --somatic-length 0 --panel-length 0 --no-single-pass --no-configs3 ${BENCH_ARGS}"
 run() { "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step rc=$rc: $*"; exit $rc; fi; }
 run timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $B > $OUT/trace.log 2>&1
 i=0

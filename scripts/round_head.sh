@@ -8,8 +8,8 @@ OUT=$1
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 420 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/gpu_tests.log 2>&1
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-single-pass > $OUT/trace.log 2>&1
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-single-pass > $OUT/trace.log 2>&1
 timeout -k 10 120 python3 -c "
 import sys; sys.path.insert(0, '.')
 from guacamole_amd import synthetic

@@ -94,7 +94,7 @@ def test_plain_bench_gpus_two_launches_its_ranks():
     env = dict(os.environ, GQ_DIST_BACKEND="gloo", PYTHONPATH=ROOT)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--length", "2000000", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--length", "2000000", "--steps", "2", "--warmup", "1", "--full",
            "--somatic-length", "0", "--panel-length", "0", "--no-cpu-baseline", "--no-configs3"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
