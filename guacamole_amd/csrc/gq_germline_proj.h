@@ -1,6 +1,6 @@
 // gq_germline_proj.h — germline_proj: the germline-threshold pileup kernel over the read
-// projections derived at upload (proj rows, pev: gq_pileup.hip row_count / proj_fill /
-// pev_fill).
+// projections derived at upload (proj rows, pev: gq_pileup.hip row_count /
+// proj_fill_cells / pev_fill).
 //
 // One WAVE per 512-locus tile, no workgroup barriers: tiles are aligned to 512-locus blocks
 // (plan(..., aligned)), so lane l owns the 8-locus column [B0 + 8l, B0 + 8l + 8) of its tile's

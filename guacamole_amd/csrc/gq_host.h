@@ -533,13 +533,13 @@ __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
 // consecutive words of a piece on consecutive lanes, so the loads of a piece's bases and the
 // stores of its row coalesce): raw = fetch(read, meta, column, events) (the word's loads), then
 // emit(act, raw, read, meta, column, events).  events: the word's eight MD-event bits (EV only).
-// Each lane takes kU words per round and issues all their loads before the first emit.  A word
-// finds its piece without a search: the pieces starting inside the round's words mark their first
-// word in LDS (owner), a prefix maximum carries each mark over the piece's words, and one ballot
-// gives the piece already running at each 64-word window's start.  setup(read, meta, md_off)
-// runs once per piece on the piece's lane (meta's read fields filled) and returns false to drop it.  meta: this wave's 64 LDS entries;
-// owner: its kU * 64 LDS words.
-template <bool EV, int kU, class S, class F, class E>
+// Each lane takes one word per round.  A word finds its piece without a search: the pieces
+// starting inside the round's words mark their first word in LDS (owner), a prefix maximum
+// carries each mark over the piece's words, and one ballot gives the piece already running at
+// the 64-word window's start.  setup(read, meta, md_off) runs once per piece on the piece's lane
+// (meta's read fields filled) and returns false to drop it.  meta: this wave's 64 LDS entries;
+// owner: its 64 LDS words.
+template <bool EV, class S, class F, class E>
 __device__ __forceinline__ void slice_fill(const DevReads &R, const SliceWin &W, const uint16_t *__restrict__ rows,
                                            PieceMeta *__restrict__ meta, uint32_t *__restrict__ owner, S &&setup,
                                            F &&fetch, E &&emit) {
@@ -580,62 +580,49 @@ __device__ __forceinline__ void slice_fill(const DevReads &R, const SliceWin &W,
     const uint32_t len = (uint32_t)sl;
     const uint32_t incl = wave_incl_scan(len), ex = incl - len;
     const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    for (uint32_t w0 = 0; w0 < tot; w0 += 64 * kU) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) owner[64 * u + lane] = 0;
+    for (uint32_t w0 = 0; w0 < tot; w0 += 64) {
+      owner[lane] = 0;
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      if (len > 0 && ex > w0 && ex < w0 + 64 * kU) owner[ex - w0] = (uint32_t)lane + 1;  // the piece's first word
+      if (len > 0 && ex > w0 && ex < w0 + 64) owner[ex - w0] = (uint32_t)lane + 1;  // the piece's first word
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      int kk[kU];
-      int32_t col[kU];
-      bool act[kU];
-      PieceMeta pm[kU];
-      uint32_t evb[kU];
-      decltype(fetch((int64_t)0, pm[0], (int32_t)0, 0u)) raw[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const uint32_t wb = w0 + 64 * u, w = wb + (uint32_t)lane;
-        const unsigned long long run = __ballot(len > 0 && ex <= wb);  // the last of them runs at wb
-        const uint32_t k_at = run ? 64u - (uint32_t)__clzll((long long)run) : 0u;  // its lane + 1
-        const uint32_t k1 = max(wave_incl_max(owner[64 * u + lane]), k_at);
-        act[u] = w < tot;
-        const int k = act[u] ? (int)k1 - 1 : 0;
-        kk[u] = k;
-        const uint4 *src = reinterpret_cast<const uint4 *>(meta + k);
-        const uint4 a = src[0], b = src[1];
-        PieceMeta &m = pm[u];
-        m.p0 = (int64_t)((uint64_t)a.x | ((uint64_t)a.y << 32));
-        m.s = (int32_t)a.z;
-        m.e = (int32_t)a.w;
-        m.s0 = (int32_t)b.x;
-        m.row = (int32_t)b.y;
-        m.info = b.z;
-        m.mq = b.w;
-        const uint32_t kex = (uint32_t)__shfl((int)ex, k, 64);
-        col[u] = m.s0 + (int32_t)(w - kex);
-        evb[u] = 0;
-        if constexpr (EV) {
-          const uint4 c = src[2];
-          const int32_t i0 = 8 * (col[u] - m.s0);  // bit of the word's first locus
-          const int iw = i0 >> 5;
-          const uint32_t ew = (iw & 2) ? ((iw & 1) ? c.w : c.z) : ((iw & 1) ? c.y : c.x);
-          evb[u] = (ew >> (i0 & 31)) & 0xFFu;
-        }
+      const uint32_t w = w0 + (uint32_t)lane;
+      const unsigned long long run = __ballot(len > 0 && ex <= w0);  // the last of them runs at w0
+      const uint32_t k_at = run ? 64u - (uint32_t)__clzll((long long)run) : 0u;  // its lane + 1
+      const uint32_t k1 = max(wave_incl_max(owner[lane]), k_at);
+      const bool act = w < tot;
+      const int k = act ? (int)k1 - 1 : 0;
+      const uint4 *src = reinterpret_cast<const uint4 *>(meta + k);
+      const uint4 a = src[0], b = src[1];
+      PieceMeta m;
+      m.p0 = (int64_t)((uint64_t)a.x | ((uint64_t)a.y << 32));
+      m.s = (int32_t)a.z;
+      m.e = (int32_t)a.w;
+      m.s0 = (int32_t)b.x;
+      m.row = (int32_t)b.y;
+      m.info = b.z;
+      m.mq = b.w;
+      const uint32_t kex = (uint32_t)__shfl((int)ex, k, 64);
+      const int32_t col = m.s0 + (int32_t)(w - kex);
+      uint32_t evb = 0;
+      if constexpr (EV) {
+        const uint4 c = src[2];
+        const int32_t i0 = 8 * (col - m.s0);  // bit of the word's first locus
+        const int iw = i0 >> 5;
+        const uint32_t ew = (iw & 2) ? ((iw & 1) ? c.w : c.z) : ((iw & 1) ? c.y : c.x);
+        evb = (ew >> (i0 & 31)) & 0xFFu;
       }
-#pragma unroll
-      for (int u = 0; u < kU; ++u)
-        if (act[u]) raw[u] = fetch(r0 + kk[u], pm[u], col[u], evb[u]);
-#pragma unroll
-      for (int u = 0; u < kU; ++u) emit(act[u], raw[u], r0 + kk[u], pm[u], col[u], evb[u]);
+      decltype(fetch((int64_t)0, m, (int32_t)0, 0u)) raw;
+      if (act) raw = fetch(r0 + k, m, col, evb);
+      emit(act, raw, r0 + k, m, col, evb);
     }
     __builtin_amdgcn_wave_barrier();  // (the next batch rewrites meta)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   }
 }
 
-// ---- Projection words (proj_fill / proj_fill_rw and the somatic fused fill) ----
+// ---- Projection words (proj_fill_cells' slow path and proj_fill_deep) ----
 // A general CIGAR's count segments (col_derive): Match/Mismatch runs, complex runs, MidDeletion runs.
 constexpr uint32_t kSegCount = 0, kSegComplex = 1, kSegMidDel = 2;
 __device__ __forceinline__ uint32_t proj_code(uint8_t b) {  // A 1, C 3, T 4, G 7; N and the rest 0
@@ -703,176 +690,23 @@ __device__ __forceinline__ ProjRaw proj_fetch(const DevReads &R, int64_t r, cons
 // wrapped pool in another order, or past 2 GiB of it): its cells take the slow path.
 constexpr uint32_t kCell3Far = 0x80000000u;
 
-// ---- Piece fills: a wave per slice, a lane per piece, rows built in LDS (A/B: GQ_FILL=pieces) ----
-// A wave takes a slice: each lane takes one of its window reads and, if the read has a piece in
-// the slice, issues the loads of all the piece's words at once (up to 16 columns), turns them into
-// words and writes them into the slice's rows in LDS (kPieceRows rows at a time, padded to 17
-// words per row against bank conflicts); the rows then leave LDS as whole rows, 64 consecutive
-// words per store (every word written, so the pool needs no preset).  A window over 64 reads
-// takes several batches, a slice over kPieceRows rows several row chunks.
-constexpr int kPieceRows = 64;
-constexpr int kPieceStride = 17;  // LDS words per row
-struct PieceRec {                 // a window read as one lane holds it
-  int64_t p0;                     // pool offset of locus 0 (column-eligible reads)
-  int32_t s, e;                   // [start, end)
-  uint32_t info, mq;              // ColDesc info, mapping quality
-  int64_t md_off;                 // its MD events
-  uint32_t ev[4];                 // (EV fills) its first four MD events (0xFFFFFFFF: none)
-};
-// proj_codes4 for the bytes of a column-eligible read (A C G T N only, zero outside the read):
-// A 1, C 3, G 7, T 4 are the low three bits, N (6) and zero bytes give 0.
-__device__ __forceinline__ uint32_t proj_codes4_clean(uint32_t x) {
-  const uint32_t y = x & 0x07070707u;
-  const uint32_t n = y ^ 0x06060606u;                                   // zero bytes: N
-  const uint32_t keep = (((n & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | n) & 0x80808080u;  // 0x80: not N
-  return y & ((keep >> 7) * 0xFFu);
-}
-__device__ __forceinline__ PieceMeta piece_rec_meta(const PieceRec &m) {
-  PieceMeta p;
-  p.p0 = m.p0;
-  p.s = m.s;
-  p.e = m.e;
-  p.s0 = 0;
-  p.row = 0;
-  p.info = m.info;
-  p.mq = m.mq;
-  return p;
-}
-
-// For every slice (grid-stride over waves): for each row chunk, rows zeroed in `lds` (words of
-// type T, `zero`), then each window read r with a piece whose row lies in the chunk:
-//   keep(rec)                      false: the piece writes nothing (its cells keep `zero`);
-//   fast(rec, col, raw) for each of its columns, all issued before any is used (false: that
-//                                  word takes slow(rec, r, col) instead, out of the unrolled path);
-//   word(rec, col, raw) -> T       the word;
-// then the chunk's rows go to pool (T words, 16 per row) at the slice's rows.  done(slot, flag)
-// closes the slice with the OR over its lanes of flag(word) (e.g. a kMargin8None term).  pbad
-// slices get `zero` rows.
-template <class T, class Raw, bool EV, class K, class F, class Wd, class S, class G, class D>
-__device__ __forceinline__ void piece_fill(const DevReads &R, int64_t n_slices, T *__restrict__ lds, T *__restrict__ pool,
-                                           T zero, K &&keep, F &&fast, Wd &&word, S &&slow, G &&flag, D &&done) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t slot = wave_id(); slot < n_slices; slot += nw) {
-    const int64_t g0 = R.srow[slot];
-    const int32_t nr = (int32_t)(R.srow[slot + 1] - g0);
-    if (nr <= 0) continue;
-    T *out = pool + 16 * g0;
-    if (R.pbad[slot]) {
-      for (int32_t c = lane; c < 16 * nr; c += 64) out[c] = zero;
-      continue;
-    }
-    const SliceWin W = slice_stored(R, slot);
-    const uint16_t *prw = R.prow + R.soff[slot];
-    bool any = false;
-    for (int32_t k0 = 0; k0 < nr; k0 += kPieceRows) {
-      const int32_t nk = nr - k0 < kPieceRows ? nr - k0 : kPieceRows;
-      for (int32_t c = lane; c < kPieceStride * nk; c += 64) lds[c] = zero;
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      for (int64_t r0 = W.ra; r0 < W.rz; r0 += 64) {
-        const int64_t r = r0 + lane;
-        const bool in = r < W.rz;
-        const int64_t rr = in ? r : W.ra;
-        const int32_t row = in ? (int32_t)prw[rr - W.ra] : 0xFFFF;
-        const ProjRec pr = R.prec[rr];
-        const ColDesc d = R.cdesc[rr];
-        const int32_t ld = R.lead[rr];
-        const int64_t so = R.seq_off[rr];
-        PieceRec m;
-        m.mq = R.mapq[rr];
-        m.md_off = R.md_off[rr];
-        m.p0 = so + (ld > 0 ? ld : 0) - d.start;
-        m.s = d.start;
-        m.e = d.end;
-        m.info = d.info;
-        int32_t s0 = W.qc0, sl = 0;
-        piece_of(pr, W.qc0, s0, sl);
-        const bool mine = in && row != 0xFFFF && row >= k0 && row < k0 + nk && sl > 0 && keep(m);
-        if (!__ballot(mine)) continue;
-        if constexpr (EV) {
-          const int32_t nmd = (int32_t)(m.info & 0xFFFFu);
-          const uint32_t *ev = R.md_ev + m.md_off;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) m.ev[q] = mine && q < nmd ? ev[q] : 0xFFFFFFFFu;
-        }
-        const int32_t c0 = s0 - W.qc0;
-        T *lrow = lds + kPieceStride * (mine ? row - k0 : 0);
-        uint32_t sm = 0;
-        const int32_t nj = mine ? sl : 0;
-        for (int32_t j0 = 0; __ballot(j0 < nj); j0 += 4) {  // four words at a time, their loads together
-          Raw raw[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            raw[j] = Raw{};
-            if (j0 + j < nj && !fast(m, s0 + j0 + j, raw[j])) sm |= 1u << (j0 + j);
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + j < nj && !((sm >> (j0 + j)) & 1u)) lrow[c0 + j0 + j] = word(m, s0 + j0 + j, raw[j]);
-        }
-#pragma unroll 1
-        for (int j = 0; j < 16; ++j)  // the rare words off the fast path, one copy of their code
-          if (mine && ((sm >> j) & 1u)) lrow[c0 + j] = slow(m, r, s0 + j);
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      T *o = out + 16 * k0;
-      for (int32_t c = lane; c < 16 * nk; c += 64) {
-        const T w = lds[kPieceStride * (c >> 4) + (c & 15)];
-        o[c] = w;
-        any = any || flag(w);
-      }
-      __builtin_amdgcn_wave_barrier();  // (the next chunk rezeroes the rows)
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    done(slot, __ballot(any) != 0);
-  }
-}
-
-// ---- Read-major fills (the default; slice_fill above is the A/B alternative, GQ_FILL=slice) ----
-inline int fill_dbg() {  // GQ_FILL_DBG (read_fill): diagnostics and the XCD-contiguous order
+// ---- The read-major fill (the margin projection's, mproj_fill_rw) ----
+inline int fill_dbg() {  // GQ_FILL_DBG (proj_fill_cells, read_fill): diagnostics and the XCD-contiguous order
   static const int v = getenv("GQ_FILL_DBG") ? atoi(getenv("GQ_FILL_DBG")) : 0;
   return v;
 }
-inline bool fill_slice_major() {
-  static const bool v = getenv("GQ_FILL") && strcmp(getenv("GQ_FILL"), "slice") == 0;
-  return v;
-}
-// The cell / piece fills (a wave per slice, a lane per cell / piece) are the default; GQ_FILL=rw / slice: the
-// read-major / slice-major fills of round 4 (A/B alternatives).
-inline bool fill_pieces() {  // the cell or piece fills (no preset of the pool)
-  static const bool v = !getenv("GQ_FILL") || strcmp(getenv("GQ_FILL"), "pieces") == 0 ||
-                        strcmp(getenv("GQ_FILL"), "cells") == 0 || strcmp(getenv("GQ_FILL"), "cellsb") == 0;
-  return v;
-}
-inline int fill_mode() {  // 0: cells (the projection's default), 1: pieces (GQ_FILL=pieces), 2: a workgroup per slice (cellsb)
-  static const int v = getenv("GQ_FILL") && strcmp(getenv("GQ_FILL"), "pieces") == 0   ? 1
-                       : getenv("GQ_FILL") && strcmp(getenv("GQ_FILL"), "cellsb") == 0 ? 2
-                                                                                        : 0;
-  return v;
-}
-// The margin projection's fill: read-major by default (chr20 60x: 5.5 ms against 8.6 ms by cells
-// and 15.7 ms by pieces); GQ_MFILL=cells / pieces / slice pick the others.
-inline int margin_fill_mode() {  // 0 read-major, 1 cells, 2 pieces, 3 slice-major
-  static const int v = !getenv("GQ_MFILL") ? 0
-                       : strcmp(getenv("GQ_MFILL"), "cells") == 0 ? 1
-                       : strcmp(getenv("GQ_MFILL"), "pieces") == 0 ? 2
-                       : strcmp(getenv("GQ_MFILL"), "slice") == 0 ? 3 : 0;
-  return v;
-}
 // One wave per batch of 64 consecutive reads, a lane per word of the batch's projections: a
-// read's words (its columns [col0, col1)) sit on consecutive lanes in column order, so its bases /
+// read's words (its columns [col0, col1)) sit on consecutive lanes in column order, so its
 // qualities load as one contiguous run and each of its pieces' words lands in one row segment.
 // No slice window is walked: each read looks up its pieces' rows once (the rows row_count stored
 // per (slice, window read)) and keeps their global row numbers in its LDS record, so a round of
-// words has no dependent record loads.  kU rounds' loads are issued before the first store.
+// words has no dependent record loads.
 struct __attribute__((aligned(16))) ReadMeta {
   int64_t p0;         // pool offset of locus 0 (column-eligible reads: base / quality of locus l at p0 + l)
   int32_t s, e;       // the read's [start, end)
   uint32_t info, mq;  // ColDesc info, mapping quality
   int32_t col0;       // first column
-  uint32_t evin;      // 1: its MD events are all in ev01 / ev23 (read_fill<true>), else at md_off
+  uint32_t evin;      // 1: its MD events are all in ev01 / ev23, else at md_off
   int64_t md_off;     // its MD events
   int64_t qoff;       // its contig's first slice
   int64_t grow[3];    // global row of its first three pieces (-1: no row / pbad slice)
@@ -930,17 +764,15 @@ __device__ __forceinline__ void piece_grows(const DevReads &R, int64_t r, int64_
 // Batches of 64 reads from batch b0 on, stride nb (grid-stride over waves).  For each word of
 // each kept read: raw = fetch(read, meta, column) (its loads), then emit(act, raw, read, meta,
 // column, grow, slot).  keep(meta) decides per read (false: no words); batch(first read) runs
-// at each batch's start (every lane).  meta: this wave's 64 LDS records; owner: its kU * 64 LDS
-// words.
+// at each batch's start (every lane).  meta: this wave's 64 LDS records; owner: its 64 LDS
+// words.  Each read's MD events (up to four) are loaded with its records into ev01 / ev23.
 // dbg (diagnostics, GQ_FILL_DBG; the pool is wrong when set): 1 no word loads, 2 no word stores;
 // 4: XCD-contiguous batches (workgroup i runs on XCD i % 8: each XCD takes one contiguous
 // eighth of the batches, so rows that pieces of neighbouring batches share meet in one L2).
-// EV: each read's MD events (up to four) are loaded with its records into ev01 / ev23.
-// kW: consecutive words of a read per lane (the lane-to-word mapping is done once per kW words).
 // src (R.seq or R.qual; nullptr: none): fetch(read, meta, column, pre, fast) gets the word's
 // eight bytes at src + p0 + 8 column already loaded when fast (a column-eligible read's word
 // inside the pool).
-template <int kU, bool EV, int kW, class B, class K, class F, class E>
+template <class B, class K, class F, class E>
 __device__ __forceinline__ void read_fill(const DevReads &R, ReadMeta *__restrict__ meta, uint32_t *__restrict__ owner,
                                           int dbg, const uint8_t *src, B &&batch, K &&keep, F &&fetch, E &&emit) {
   const int lane = threadIdx.x & 63;
@@ -980,34 +812,31 @@ __device__ __forceinline__ void read_fill(const DevReads &R, ReadMeta *__restric
     m.evin = 0;
     m.ev01 = m.ev23 = 0xFFFFFFFFu;
     m.md_off = mdo;
-    if constexpr (EV) {
-      const int32_t nmd = (int32_t)(d.info & 0xFFFFu);
-      if (in && nmd <= 4 && d.end - d.start < 0xFFF0) {  // (no word of the read reaches the 0xFFFF marker)
-        // (the four loads issued together: past the read's last event its last one again)
-        uint32_t v[4];
-        if (nmd > 0) {
+    const int32_t nmd = (int32_t)(d.info & 0xFFFFu);
+    if (in && nmd <= 4 && d.end - d.start < 0xFFF0) {  // (no word of the read reaches the 0xFFFF marker)
+      // (the four loads issued together: past the read's last event its last one again)
+      uint32_t v[4];
+      if (nmd > 0) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) v[k] = R.md_ev[mdo + (k < nmd ? k : nmd - 1)];
-        }
+        for (int k = 0; k < 4; ++k) v[k] = R.md_ev[mdo + (k < nmd ? k : nmd - 1)];
+      }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = k < nmd ? v[k] : 0xFFFFFFFFu;
-        uint32_t o[4];
+      for (int k = 0; k < 4; ++k) v[k] = k < nmd ? v[k] : 0xFFFFFFFFu;
+      uint32_t o[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = v[k] >> 8;  // offsets (none: 0xFFFFFF)
-        bool ok = true;
+      for (int k = 0; k < 4; ++k) o[k] = v[k] >> 8;  // offsets (none: 0xFFFFFF)
+      bool ok = true;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ok = ok && (k >= nmd || o[k] < 0xFFFFu);
-        if (ok) {
-          m.evin = 1;
-          m.ev01 = (o[0] & 0xFFFFu) | ((o[1] & 0xFFFFu) << 16);
-          m.ev23 = (o[2] & 0xFFFFu) | ((o[3] & 0xFFFFu) << 16);
-        }
+      for (int k = 0; k < 4; ++k) ok = ok && (k >= nmd || o[k] < 0xFFFFu);
+      if (ok) {
+        m.evin = 1;
+        m.ev01 = (o[0] & 0xFFFFu) | ((o[1] & 0xFFFFu) << 16);
+        m.ev23 = (o[2] & 0xFFFFu) | ((o[3] & 0xFFFFu) << 16);
       }
     }
     m.qoff = R.qoff[lo];
-    uint32_t len = in && pr.col1 != kProjNone && pr.col1 > pr.col0 ? (uint32_t)(pr.col1 - pr.col0) : 0u;
+    uint32_t len = in && pr.col1 != kProjNone && pr.col1 > pr.col0 ? (uint32_t)(pr.col1 - pr.col0) : 0u;  // its words
     if (len && !keep(m)) len = 0;
-    const uint32_t nun = (len + (uint32_t)kW - 1u) / (uint32_t)kW;  // the read's lane units
     {
       const int64_t q0 = m.qoff + (pr.col0 >> 4);
       const int32_t npc = len ? ((pr.col1 - 1) >> 4) - (pr.col0 >> 4) + 1 : 0;
@@ -1017,89 +846,58 @@ __device__ __forceinline__ void read_fill(const DevReads &R, ReadMeta *__restric
       for (int j = 0; j < kReadPieces; ++j) m.grow[j] = g[j];
     }
     if (len) meta[lane] = m;
-    const uint32_t incl = wave_incl_scan(nun), ex = incl - nun;
+    const uint32_t incl = wave_incl_scan(len), ex = incl - len;
     const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    for (uint32_t w0 = 0; w0 < tot; w0 += 64 * kU) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) owner[64 * u + lane] = 0;
+    for (uint32_t w0 = 0; w0 < tot; w0 += 64) {
+      owner[lane] = 0;
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      if (nun > 0 && ex > w0 && ex < w0 + 64 * kU) owner[ex - w0] = (uint32_t)lane + 1;  // the read's first unit
+      if (len > 0 && ex > w0 && ex < w0 + 64) owner[ex - w0] = (uint32_t)lane + 1;  // the read's first word
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      constexpr int N = kU * kW;
-      int kk[N];
-      int32_t col[N];
-      bool act[N];
-      int64_t grow[N], slot[N];
-      ReadMeta pm[kU];
-      decltype(fetch((int64_t)0, pm[0], (int32_t)0, 0ull, false)) raw[N];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const uint32_t wb = w0 + 64 * u, w = wb + (uint32_t)lane;
-        const unsigned long long run = __ballot(nun > 0 && ex <= wb);  // the last of them runs at wb
-        const uint32_t k_at = run ? 64u - (uint32_t)__clzll((long long)run) : 0u;  // its lane + 1
-        const uint32_t k1 = max(wave_incl_max(owner[64 * u + lane]), k_at);
-        const bool au = w < tot;
-        const int k = au ? (int)k1 - 1 : 0;
-        const uint4 *src = reinterpret_cast<const uint4 *>(meta + k);
-        const uint4 a = src[0], bq = src[1], c = src[2], dq = src[3], eq = src[4];
-        ReadMeta &mm = pm[u];
-        mm.p0 = (int64_t)((uint64_t)a.x | ((uint64_t)a.y << 32));
-        mm.s = (int32_t)a.z;
-        mm.e = (int32_t)a.w;
-        mm.info = bq.x;
-        mm.mq = bq.y;
-        mm.col0 = (int32_t)bq.z;
-        mm.evin = bq.w;
-        mm.ev01 = eq.z;
-        mm.ev23 = eq.w;
-        mm.md_off = (int64_t)((uint64_t)c.x | ((uint64_t)c.y << 32));
-        mm.qoff = (int64_t)((uint64_t)c.z | ((uint64_t)c.w << 32));
-        const int64_t g0 = (int64_t)((uint64_t)dq.x | ((uint64_t)dq.y << 32));
-        const int64_t g1 = (int64_t)((uint64_t)dq.z | ((uint64_t)dq.w << 32));
-        const int64_t g2 = (int64_t)((uint64_t)eq.x | ((uint64_t)eq.y << 32));
-        const uint32_t kex = (uint32_t)__shfl((int)ex, k, 64);
-        const int32_t cbase = mm.col0 + kW * (int32_t)(w - kex);
-        const int32_t col1 = (mm.e + 7) >> 3;  // the read's column end (prec_fill)
-#pragma unroll
-        for (int q = 0; q < kW; ++q) {
-          const int i = kW * u + q;
-          kk[i] = k;
-          col[i] = cbase + q;
-          act[i] = au && col[i] < col1;
-          const int32_t pj = (col[i] >> 4) - (mm.col0 >> 4);
-          slot[i] = mm.qoff + (col[i] >> 4);
-          grow[i] = pj == 0 ? g0 : pj == 1 ? g1 : pj == 2 ? g2 : -2;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        if (act[i] && grow[i] == -2) grow[i] = piece_grow(R, 64 * b + kk[i], slot[i]);  // a long read's later piece
-        act[i] = act[i] && grow[i] >= 0;
-      }
-      // The N words' 8-byte loads first, every lane's (a word off the fast path loads src[0],
+      const uint32_t w = w0 + (uint32_t)lane;
+      const unsigned long long run = __ballot(len > 0 && ex <= w0);  // the last of them runs at w0
+      const uint32_t k_at = run ? 64u - (uint32_t)__clzll((long long)run) : 0u;  // its lane + 1
+      const uint32_t k1 = max(wave_incl_max(owner[lane]), k_at);
+      const bool au = w < tot;
+      const int k = au ? (int)k1 - 1 : 0;
+      const uint4 *rec = reinterpret_cast<const uint4 *>(meta + k);
+      const uint4 a = rec[0], bq = rec[1], c = rec[2], dq = rec[3], eq = rec[4];
+      ReadMeta mm;
+      mm.p0 = (int64_t)((uint64_t)a.x | ((uint64_t)a.y << 32));
+      mm.s = (int32_t)a.z;
+      mm.e = (int32_t)a.w;
+      mm.info = bq.x;
+      mm.mq = bq.y;
+      mm.col0 = (int32_t)bq.z;
+      mm.evin = bq.w;
+      mm.ev01 = eq.z;
+      mm.ev23 = eq.w;
+      mm.md_off = (int64_t)((uint64_t)c.x | ((uint64_t)c.y << 32));
+      mm.qoff = (int64_t)((uint64_t)c.z | ((uint64_t)c.w << 32));
+      const int64_t g0 = (int64_t)((uint64_t)dq.x | ((uint64_t)dq.y << 32));
+      const int64_t g1 = (int64_t)((uint64_t)dq.z | ((uint64_t)dq.w << 32));
+      const int64_t g2 = (int64_t)((uint64_t)eq.x | ((uint64_t)eq.y << 32));
+      const uint32_t kex = (uint32_t)__shfl((int)ex, k, 64);
+      const int32_t col = mm.col0 + (int32_t)(w - kex);
+      const int32_t col1 = (mm.e + 7) >> 3;  // the read's column end (prec_fill)
+      bool act = au && col < col1;
+      const int32_t pj = (col >> 4) - (mm.col0 >> 4);
+      const int64_t slot = mm.qoff + (col >> 4);
+      int64_t grow = pj == 0 ? g0 : pj == 1 ? g1 : pj == 2 ? g2 : -2;
+      if (act && grow == -2) grow = piece_grow(R, 64 * b + k, slot);  // a long read's later piece
+      act = act && grow >= 0;
+      // The word's 8-byte load first, every lane's (a word off the fast path loads src[0],
       // unused): a load under a per-word branch, or its mask applied right after it, would make
-      // the wave wait for each before issuing the next.
-      uint64_t pre[N];
-      bool fast[N];
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        const ReadMeta &mi = pm[i / kW];
-        const int64_t a = mi.p0 + 8 * (int64_t)col[i];
-        fast[i] = src != nullptr && act[i] && (mi.info & kColEligible) && a >= 0 && a + 8 <= R.seq_cap;
-        pre[i] = src != nullptr && R.seq_cap >= 8 && !(dbg & 1)
-                     ? *reinterpret_cast<const gq_u64u *>(src + (fast[i] ? a : 0))
-                     : 0ull;
-      }
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        if (act[i] && !(dbg & 1)) raw[i] = fetch(64 * b + kk[i], pm[i / kW], col[i], pre[i], fast[i]);
-        else raw[i] = {};
-      }
-#pragma unroll
-      for (int i = 0; i < N; ++i)
-        emit(act[i] && !(dbg & 2), raw[i], 64 * b + kk[i], pm[i / kW], col[i], grow[i], slot[i]);
+      // the wave wait for it.
+      const int64_t pa = mm.p0 + 8 * (int64_t)col;
+      const bool fast = src != nullptr && act && (mm.info & kColEligible) && pa >= 0 && pa + 8 <= R.seq_cap;
+      const uint64_t pre = src != nullptr && R.seq_cap >= 8 && !(dbg & 1)
+                               ? *reinterpret_cast<const gq_u64u *>(src + (fast ? pa : 0))
+                               : 0ull;
+      decltype(fetch((int64_t)0, mm, (int32_t)0, 0ull, false)) raw{};
+      if (act && !(dbg & 1)) raw = fetch(64 * b + k, mm, col, pre, fast);
+      emit(act && !(dbg & 2), raw, 64 * b + k, mm, col, grow, slot);
     }
     __builtin_amdgcn_wave_barrier();  // (the next batch rewrites meta)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1186,7 +984,7 @@ struct DevBuf {
 struct gq_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[6] = {};
   hipEvent_t dev_ev[4] = {};  // the derivation's device spans (gq_reads_info: derive / projection / fill)
   // a second stream for derivation kernels independent of the main stream's (the pool scan beside
   // the read checks, the sparse entries beside the projection fill), joined by side_ev
@@ -1207,9 +1005,7 @@ struct gq_ctx {
   gq::DevBuf amb, amb_ref, heap_off, heap_reads;  // heap-order reference bases (heap_ref_bases)
   gq::DevBuf win_meta, win_grp;                    // somatic pileup element order (window_first / _group)
   gq::DevBuf deep_list, deep_scratch;              // somatic: the deep caller's list and per-wave scratch
-  int front_wg_per_cu = 0;                         // somatic_front: resident workgroups per CU
   gq::DevBuf cands;                                // somatic: the candidates' records (CandRec)
-  gq::DevBuf el_store;                             // somatic: the split caller's element store (ElemStore)
   gq::DevBuf win_bound;                            // germline: window bounds (window_bounds)
   gq::DevBuf bkt;                                  // germline output order: bucket counts / offsets / fill
   // The bulk host -> device staging (H2DStager): two pinned chunks kept for the context's life
@@ -1404,16 +1200,7 @@ gq_status ensure_columns(gq_ctx *c, const gq_dev_reads *d);
 // ev_rb (the read base under each MD event) of a resident read set, derived on first use
 gq_status ensure_ev_bases(gq_ctx *c, const gq_dev_reads *d);
 // The projection (ProjRec) of a resident read set, derived on first use.
-// A margin projection wanted with the projection (the somatic tumor, germline-standard): with
-// GQ_FILL_ONE both are filled in one read-major pass (fused_projection_fill) when the projection
-// is derived — an A/B alternative: at chr20 60x it took 9.0 ms against 2.8 + 5.6 ms for the two
-// passes, so the default keeps them separate.
-struct MarginReq {
-  int min_mapq;
-  bool incl_align;
-};
-gq_status ensure_projection(gq_ctx *c, const gq_dev_reads *d, const MarginReq *mr = nullptr);
-gq_status fused_projection_fill(gq_ctx *c, const gq_dev_reads *d, uint8_t *proj_pool, const MarginReq &mr);
+gq_status ensure_projection(gq_ctx *c, const gq_dev_reads *d);
 // No-op launches that load each translation unit's code object onto the device (gq_open's prep).
 hipError_t warm_pileup(hipStream_t s);
 hipError_t warm_somatic(hipStream_t s);

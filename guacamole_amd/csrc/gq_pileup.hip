@@ -484,53 +484,6 @@ __global__ void rows64(int64_t n, const int32_t *__restrict__ srows, int64_t *__
   if (q <= n) out[q] = q < n ? srows[q] : 0;
 }
 
-// The projection pool in block rows, one wave per slice, a lane per word (the rows row_count
-// assigned, stored; pbad slices stay zero: their blocks go to the walker).
-// KU: words per lane per round (GQ_FILL_U picks 1 or 4: fewer registers and more waves, or more
-// loads in flight per wave; measured at chr20 60x: 1 word 4.8 ms, 4 words 5.8 ms, so 1 is the default)
-template <int KU>
-__global__ __launch_bounds__(256) void proj_fill(DevReads R, int64_t n_slices, uint8_t *__restrict__ proj) {
-  __shared__ PieceMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][KU * 64];
-  PieceMeta *meta = s_meta[threadIdx.x >> 6];
-  uint32_t *owner = s_owner[threadIdx.x >> 6];
-  const int64_t w0 = wave_id();
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t slot = w0; slot < n_slices; slot += nw) {
-    if (R.pbad[slot]) continue;  // uniform
-    uint32_t *out = reinterpret_cast<uint32_t *>(proj) + 16 * R.srow[slot];  // the slice's block rows
-    slice_fill<false, KU>(
-        R, slice_stored(R, slot), R.prow + R.soff[slot], meta, owner,
-        [&](int64_t, PieceMeta &, int64_t) { return true; },
-        [&](int64_t r, const PieceMeta &m, int32_t col, uint32_t) { return proj_fetch(R, r, m, col); },
-        [&](bool act, const ProjRaw &x, int64_t, const PieceMeta &m, int32_t col, uint32_t) {
-          if (act)
-            out[16 * (int64_t)m.row + (col & 15)] =
-                x.gen ? x.word : proj_codes4((uint32_t)x.b) | (proj_codes4((uint32_t)(x.b >> 32)) << 4);
-        });
-  }
-}
-
-// The projection pool, read-major (read_fill): a wave per 64 consecutive reads, a lane per word.
-template <int KU, int KW>
-__global__ __launch_bounds__(256) void proj_fill_rw(DevReads R, uint8_t *__restrict__ proj, int dbg) {
-  __shared__ ReadMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][KU * 64];
-  uint32_t *out = reinterpret_cast<uint32_t *>(proj);
-  read_fill<KU, false, KW>(
-      R, s_meta[threadIdx.x >> 6], s_owner[threadIdx.x >> 6], dbg, R.seq, [](int64_t) {},
-      [](const ReadMeta &) { return true; },
-      [&](int64_t r, const ReadMeta &m, int32_t col, uint64_t pre, bool fast) {
-        if (fast) return ProjRaw{pre & edge_mask(m.s - 8 * col, m.e - 8 * col), 0u, 0u};
-        return proj_fetch(R, r, piece_meta(m), col);
-      },
-      [&](bool act, const ProjRaw &x, int64_t, const ReadMeta &, int32_t col, int64_t grow, int64_t) {
-        if (act)  // (an eligible read's bytes are A C G T N: the v_perm lookup)
-          out[16 * grow + (col & 15)] =
-              x.gen ? x.word : perm_codes4((uint32_t)x.b) | (perm_codes4((uint32_t)(x.b >> 32)) << 4);
-      });
-}
-
 // ---- The projection pool by cells (the default) ----
 // A wave per slice, a lane per cell (row k, column c) of its rows, every word written (zeros where
 // no piece lies: the pool needs no preset), 64 consecutive words per store.  The window's reads
@@ -548,10 +501,10 @@ struct __attribute__((aligned(16))) Cell3Rec {
   int32_t s, e;       // [start, end)
   uint32_t info;      // ColDesc info (bit kColEligible: the fast path)
 };
-template <int CU>  // cells per lane whose loads issue together (4; A/B GQ_FILL_U=8)
 __global__ __launch_bounds__(256) void proj_fill_cells(DevReads R, int64_t n_slices, uint8_t *__restrict__ proj,
                                                        int64_t *__restrict__ deep, unsigned long long *__restrict__ n_deep,
                                                        int dbg) {
+  constexpr int CU = 4;  // cells per lane whose loads issue together
   __shared__ Cell3Rec s_rec[4][kCell3Win];
   __shared__ uint8_t s_map[4][kCell3Rows * 16];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -681,110 +634,6 @@ __global__ __launch_bounds__(256) void proj_fill_cells(DevReads R, int64_t n_sli
   }
 }
 
-// The cell fill with a workgroup per slice (GQ_FILL=cellsb, A/B): the window's records in one
-// round (a thread per window read), the map marked by all four waves, each thread four cells.
-__global__ __launch_bounds__(256) void proj_fill_cellsb(DevReads R, int64_t n_slices, uint8_t *__restrict__ proj,
-                                                        int64_t *__restrict__ deep, unsigned long long *__restrict__ n_deep,
-                                                        int dbg) {
-  __shared__ Cell3Rec rec[kCell3Win + 1];
-  __shared__ uint8_t map[kCell3Rows * 16];
-  const int tid = threadIdx.x;
-  for (int64_t slot = blockIdx.x; slot < n_slices; slot += gridDim.x) {
-    const int64_t g0 = R.srow[slot];
-    const int32_t nr = (int32_t)(R.srow[slot + 1] - g0);
-    if (nr <= 0) continue;
-    uint32_t *out = reinterpret_cast<uint32_t *>(proj) + 16 * g0;
-    const SliceWin W = slice_stored(R, slot);
-    const int32_t nwin = (int32_t)(W.rz - W.ra);
-    if (R.pbad[slot] || nwin > kCell3Win || nwin <= 0) {
-      for (int32_t c = tid; c < 16 * nr; c += 256) out[c] = 0u;
-      if (!R.pbad[slot] && nwin > kCell3Win && tid == 0) deep[atomicAdd(n_deep, 1ull)] = slot;
-      continue;
-    }
-    const int64_t base = R.seq_off[W.ra];
-    const uint8_t *pool = R.seq + base;
-    const int64_t span = R.seq_cap - base;
-    int32_t prow_i = 0xFFFF, pc0 = 0, psl = 0;
-    if (tid < nwin) {
-      const int64_t r = W.ra + tid;
-      const ColDesc d = R.cdesc[r];
-      const int32_t ld = R.lead[r];
-      const int64_t so = R.seq_off[r];
-      const ProjRec pr = R.prec[r];
-      const int32_t row = R.prow[R.soff[slot] + tid];
-      const int64_t av = so + (ld > 0 ? ld : 0) - base;
-      Cell3Rec m;
-      m.a = R.pool_ordered && av >= 0 && av < (int64_t)kCell3Far ? (uint32_t)av : kCell3Far;
-      m.s = d.start;
-      m.e = d.end;
-      m.info = d.info;
-      rec[tid] = m;
-      int32_t s0, sl;
-      piece_of(pr, W.qc0, s0, sl);
-      prow_i = row;
-      pc0 = s0 - W.qc0;
-      psl = row == 0xFFFF ? 0 : sl;
-    }
-    for (int32_t k0 = 0; k0 < nr; k0 += kCell3Rows) {
-      const int32_t nk = nr - k0 < kCell3Rows ? nr - k0 : kCell3Rows;
-      for (int32_t c = tid; c < 16 * nk; c += 256) map[c] = 0xFFu;
-      __syncthreads();
-      if (psl > 0 && prow_i >= k0 && prow_i < k0 + nk) {
-        uint8_t *mp = map + 16 * (prow_i - k0) + pc0;
-        for (int32_t j = 0; j < psl; ++j) mp[j] = (uint8_t)tid;
-      }
-      __syncthreads();
-      uint32_t *o = out + 16 * k0;
-      uint64_t b[4], mk[4];
-      uint32_t slow = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int32_t c = 256 * u + tid;
-        const uint32_t pp = c < 16 * nk ? map[c] : 0xFFu;
-        const Cell3Rec m = rec[pp != 0xFFu ? pp : 0];
-        const int32_t lb = 8 * (W.qc0 + (c & 15));
-        const int64_t v = (int64_t)m.a + lb - m.s;
-        const bool ok = (m.info & kColEligible) && m.a != kCell3Far && v >= 0 && v + 8 <= span;
-        if (pp != 0xFFu && !ok) slow |= 1u << u;
-        mk[u] = pp != 0xFFu && ok ? edge_mask(m.s - lb, m.e - lb) : 0ull;
-        const uint32_t off = pp != 0xFFu && ok ? (uint32_t)v : 0u;
-        b[u] = span < 8 ? (uint64_t)off : *reinterpret_cast<const gq_u64u *>(pool + off);
-      }
-      uint32_t x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint64_t y = b[u] & mk[u];
-        x[u] = perm_codes4((uint32_t)y) | (perm_codes4((uint32_t)(y >> 32)) << 4);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)  // (a wave's 64 cells lie all inside or all past 16 nk: rows padded to kRowPad)
-        if (256 * u + (tid & ~63) < 16 * nk) o[256 * u + tid] = x[u];
-      if (slow) {
-#pragma unroll 1
-        for (int u = 0; u < 4; ++u) {
-          if (!((slow >> u) & 1u)) continue;
-          const int32_t c = 256 * u + tid;
-          const uint32_t p = map[c];
-          const Cell3Rec m = rec[p];
-          const int64_t r = W.ra + p;
-          const int32_t ld = R.lead[r];
-          PieceMeta pm;
-          pm.p0 = R.seq_off[r] + (ld > 0 ? ld : 0) - m.s;
-          pm.s = m.s;
-          pm.e = m.e;
-          pm.s0 = 0;
-          pm.row = 0;
-          pm.info = m.info;
-          pm.mq = 0;
-          const ProjRaw xx = proj_fetch(R, r, pm, W.qc0 + (c & 15));
-          o[c] = xx.gen ? xx.word : proj_codes4((uint32_t)xx.b) | (proj_codes4((uint32_t)(xx.b >> 32)) << 4);
-        }
-      }
-      __syncthreads();  // (the next chunk rewrites the map, the next slice the records)
-    }
-  }
-}
-
 // The listed (deep) slices, slice-major (their rows zeroed by proj_fill_cells).
 __global__ __launch_bounds__(256) void proj_fill_deep(DevReads R, const int64_t *__restrict__ deep,
                                                       const unsigned long long *__restrict__ n_deep,
@@ -798,7 +647,7 @@ __global__ __launch_bounds__(256) void proj_fill_deep(DevReads R, const int64_t 
   for (int64_t i = wave_id(); i < nd; i += nw) {
     const int64_t slot = deep[i];
     uint32_t *out = reinterpret_cast<uint32_t *>(proj) + 16 * R.srow[slot];
-    slice_fill<false, 1>(
+    slice_fill<false>(
         R, slice_stored(R, slot), R.prow + R.soff[slot], meta, owner,
         [&](int64_t, PieceMeta &, int64_t) { return true; },
         [&](int64_t r, const PieceMeta &m, int32_t col, uint32_t) { return proj_fetch(R, r, m, col); },
@@ -808,36 +657,6 @@ __global__ __launch_bounds__(256) void proj_fill_deep(DevReads R, const int64_t 
                 x.gen ? x.word : proj_codes4((uint32_t)x.b) | (proj_codes4((uint32_t)(x.b >> 32)) << 4);
         });
   }
-}
-
-// The projection pool slice by slice (piece_fill in gq_host.h): a wave per slice, a lane per
-// piece, the rows built in LDS and written whole (zeros where no piece lies: no preset).
-__global__ __launch_bounds__(256) void proj_fill_pieces(DevReads R, int64_t n_slices, uint8_t *__restrict__ proj,
-                                                        int dbg) {
-  __shared__ uint32_t s_rows[4][kPieceRows * kPieceStride];
-  piece_fill<uint32_t, uint64_t, false>(
-      R, n_slices, s_rows[threadIdx.x >> 6], reinterpret_cast<uint32_t *>(proj), 0u,
-      [](const PieceRec &) { return true; },
-      [&](const PieceRec &m, int32_t col, uint64_t &b) {  // a column-eligible read's eight bases, one load
-        const int32_t lb = 8 * col;
-        const int64_t a = m.p0 + lb;
-        if (!(m.info & kColEligible) || a < 0 || a + 8 > R.seq_cap) return false;
-        if (dbg & 1) {  // ablation: no loads
-          b = (uint64_t)a;
-          return true;
-        }
-        b = *reinterpret_cast<const gq_u64u *>(R.seq + a);
-        if (m.s > lb || m.e < lb + 8) b &= edge_mask(m.s - lb, m.e - lb);  // (the read's first / last word)
-        return true;
-      },
-      [](const PieceRec &, int32_t, uint64_t b) {
-        return proj_codes4_clean((uint32_t)b) | (proj_codes4_clean((uint32_t)(b >> 32)) << 4);
-      },
-      [&](const PieceRec &m, int64_t r, int32_t col) {
-        const ProjRaw x = proj_fetch(R, r, piece_rec_meta(m), col);
-        return x.gen ? x.word : proj_codes4((uint32_t)x.b) | (proj_codes4((uint32_t)(x.b >> 32)) << 4);
-      },
-      [](uint32_t) { return false; }, [](int64_t, bool) {});
 }
 
 // The sparse entries of each read (thread per read): MD events, N bases (without an event),
@@ -3426,11 +3245,11 @@ gq_status gq::ensure_columns(gq_ctx *c, const gq_dev_reads *cd) {
 }
 
 // The projection of a resident read set (ProjRec in gq_kernels.h), derived on first use by a
-// kernel that reads it (germline_proj, somatic_proj over the tumor, mproj_fill): records, pbad
+// kernel that reads it (germline_proj, somatic_proj over the tumor, mproj_fill_rw): records, pbad
 // slices, each slice's read window and its pieces' rows (one greedy pass, stored), the rows'
 // offsets, the 4-bit code pool, the sparse entries.  A set no such kernel reads (the somatic
 // normal) never pays for it.
-gq_status gq::ensure_projection(gq_ctx *c, const gq_dev_reads *cd, const MarginReq *mr) {
+gq_status gq::ensure_projection(gq_ctx *c, const gq_dev_reads *cd) {
   gq_dev_reads *d = const_cast<gq_dev_reads *>(cd);
   if (d->projected) return GQ_OK;
   const auto t0 = std::chrono::steady_clock::now();
@@ -3509,12 +3328,11 @@ gq_status gq::ensure_projection(gq_ctx *c, const gq_dev_reads *cd, const MarginR
   d->d.srow = (const int64_t *)sb;
   d->d.pbad = (const uint8_t *)pbd;
   d->n_rows = tot[0];
-  // the pool: rows of 16 words, zero where no piece lies
+  // the pool: rows of 16 words, zero where no piece lies (the fill writes every word: only the
+  // 16 bytes past the rows are preset)
   const size_t pool_bytes = (size_t)kProjRowBytes * (size_t)tot[0] + 16;
   HIP_TRY(d->dp.get(&pj, pool_bytes));
-  const bool cells = fill_pieces();  // the default: every word written, no preset of the pool
-  if (cells) HIP_TRY(hipMemsetAsync((uint8_t *)pj + pool_bytes - 16, 0, 16, c->stream));
-  else HIP_TRY(hipMemsetAsync(pj, 0, pool_bytes, c->stream));
+  HIP_TRY(hipMemsetAsync((uint8_t *)pj + pool_bytes - 16, 0, 16, c->stream));
   HIP_TRY(d->dp.get(&pe, sizeof(uint2) * (size_t)(tot[1] + 1)));
   d->d.proj = (const uint8_t *)pj;
   d->d.pev = (const uint2 *)pe;
@@ -3530,60 +3348,21 @@ gq_status gq::ensure_projection(gq_ctx *c, const gq_dev_reads *cd, const MarginR
   HIP_TRY(hipEventRecord(c->side_ev[3], c->side));
   HIP_TRY(hipEventRecord(d->tev[3], c->stream));
   if (n_sl > 0) {
-    static const int fill_u = getenv("GQ_FILL_U") ? atoi(getenv("GQ_FILL_U")) : 0;
-    if (cells && fill_mode() == 2) {  // A/B: GQ_FILL=cellsb (a workgroup per slice)
-      unsigned long long *nd = nullptr;
-      int64_t *dl = nullptr;
-      HIP_TRY(d->dp.get((void **)&nd, sizeof(unsigned long long)));
-      HIP_TRY(d->dp.get((void **)&dl, sizeof(int64_t) * (size_t)n_sl));
-      HIP_TRY(hipMemsetAsync(nd, 0, sizeof(unsigned long long), c->stream));
-      const int64_t blocks = std::min<int64_t>(n_sl, 1 << 20);
-      hipLaunchKernelGGL(proj_fill_cellsb, dim3((unsigned)blocks), dim3(256), 0, c->stream, d->d, n_sl, (uint8_t *)pj,
-                         dl, nd, fill_dbg());
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(proj_fill_deep, dim3((unsigned)std::min<int64_t>(blocks, 2048)), dim3(256), 0, c->stream, d->d,
-                         (const int64_t *)dl, (const unsigned long long *)nd, (uint8_t *)pj);
-      HIP_TRY(hipGetLastError());
-      d->dp.put(nd);
-      d->dp.put(dl);
-    } else if (cells && fill_mode() == 1) {  // A/B: GQ_FILL=pieces
-      const int64_t blocks = std::min<int64_t>((n_sl + 3) / 4, 1 << 20);
-      hipLaunchKernelGGL(proj_fill_pieces, dim3((unsigned)blocks), dim3(256), 0, c->stream, d->d, n_sl, (uint8_t *)pj,
-                         fill_dbg());
-      HIP_TRY(hipGetLastError());
-    } else if (cells) {
-      unsigned long long *nd = nullptr;
-      int64_t *dl = nullptr;
-      HIP_TRY(d->dp.get((void **)&nd, sizeof(unsigned long long)));
-      HIP_TRY(d->dp.get((void **)&dl, sizeof(int64_t) * (size_t)n_sl));
-      HIP_TRY(hipMemsetAsync(nd, 0, sizeof(unsigned long long), c->stream));
-      const int64_t blocks = std::min<int64_t>((n_sl + 3) / 4, 1 << 20);
-      hipLaunchKernelGGL(fill_u == 8 ? proj_fill_cells<8> : proj_fill_cells<4>, dim3((unsigned)blocks), dim3(256), 0,
-                         c->stream, d->d, n_sl, (uint8_t *)pj, dl, nd, fill_dbg());
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(proj_fill_deep, dim3((unsigned)std::min<int64_t>(blocks, 2048)), dim3(256), 0, c->stream, d->d,
-                         (const int64_t *)dl, (const unsigned long long *)nd, (uint8_t *)pj);
-      HIP_TRY(hipGetLastError());
-      d->dp.put(nd);
-      d->dp.put(dl);
-    } else if (fill_slice_major()) {  // A/B: the slice-major fill of round 4 (GQ_FILL=slice)
-      const int64_t blocks = std::min<int64_t>((n_sl + 3) / 4, 1 << 20);
-      auto kf = fill_u == 4 ? proj_fill<4> : fill_u == 2 ? proj_fill<2> : proj_fill<1>;
-      hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(256), 0, c->stream, d->d, n_sl, (uint8_t *)pj);
-    } else if (n > 0 && mr && getenv("GQ_FILL_ONE")) {  // A/B: with the margin projection in one pass (measured slower)
-      const gq_status st = fused_projection_fill(c, d, (uint8_t *)pj, *mr);
-      if (st) return st;
-    } else if (n > 0) {
-      const int64_t blocks = (std::min<int64_t>((n + 255) / 256, 1 << 20) + 7) & ~(int64_t)7;  // a wave per 64 reads
-      static const int fill_w = getenv("GQ_FILL_W") ? atoi(getenv("GQ_FILL_W")) : 1;  // words per lane unit
-      auto kf = fill_u == 2 ? proj_fill_rw<2, 1>
-                : fill_u == 4 ? proj_fill_rw<4, 1>
-                : fill_w == 2 ? proj_fill_rw<1, 2>
-                : fill_w == 4 ? proj_fill_rw<1, 4>
-                              : proj_fill_rw<1, 1>;
-      hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(256), 0, c->stream, d->d, (uint8_t *)pj, fill_dbg());
-    }
+    // the cell fill lists the slices it leaves to the slice-major fill behind it
+    unsigned long long *nd = nullptr;
+    int64_t *dl = nullptr;
+    HIP_TRY(d->dp.get((void **)&nd, sizeof(unsigned long long)));
+    HIP_TRY(d->dp.get((void **)&dl, sizeof(int64_t) * (size_t)n_sl));
+    HIP_TRY(hipMemsetAsync(nd, 0, sizeof(unsigned long long), c->stream));
+    const int64_t blocks = std::min<int64_t>((n_sl + 3) / 4, 1 << 20);
+    hipLaunchKernelGGL(proj_fill_cells, dim3((unsigned)blocks), dim3(256), 0, c->stream, d->d, n_sl, (uint8_t *)pj, dl, nd,
+                       fill_dbg());
     HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(proj_fill_deep, dim3((unsigned)std::min<int64_t>(blocks, 2048)), dim3(256), 0, c->stream, d->d,
+                       (const int64_t *)dl, (const unsigned long long *)nd, (uint8_t *)pj);
+    HIP_TRY(hipGetLastError());
+    d->dp.put(nd);
+    d->dp.put(dl);
   }
   HIP_TRY(hipEventRecord(d->tev[4], c->stream));
   HIP_TRY(hipStreamWaitEvent(c->stream, c->side_ev[3], 0));  // (the sparse entries done)

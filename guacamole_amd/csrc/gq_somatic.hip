@@ -883,10 +883,6 @@ __device__ __forceinline__ bool allele_evidence(const DevReads &R, const Cover &
 
 constexpr int kSomWaves = kBlock / 64;
 
-#ifndef GQ_CALL_WPE
-#define GQ_CALL_WPE 3  // waves per SIMD the register budget must allow
-#endif
-
 #include "gq_somatic_call.h"
 
 // ---- germline-standard: GermlineStandard.Caller.callVariantsAtLocus
@@ -944,7 +940,7 @@ __device__ __forceinline__ GsMem gs_deep_mem(uint8_t *base, int scap, int maxG) 
 }
 
 template <bool DEEP>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1 : GQ_CALL_WPE))) void germline_standard_call(
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1 : 3))) void germline_standard_call(
     const Tile *__restrict__ tiles, const ComplexItem *__restrict__ items, DevReads R, gq_germline_std_params prm,
     SomRec *__restrict__ recs, unsigned long long rec_cap, uint8_t *__restrict__ pool, unsigned long long pool_cap,
     OutGeom og, Counters *ctr, SomWin sw, AmbItem *__restrict__ amb_out, unsigned long long amb_cap,
@@ -1257,41 +1253,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   }
 }
 
-}  // namespace (reopened below)
-
-// The projection's pool and the margin projection filled together (ensure_projection with a
-// MarginReq): the margin pool and its slice flags allocated and preset, the term table built, then
-// one pm_fill_rw pass.
-gq_status gq::fused_projection_fill(gq_ctx *c, const gq_dev_reads *t, uint8_t *proj_pool, const MarginReq &mr) {
-  const int key = 2 * mr.min_mapq + (mr.incl_align ? 1 : 0);
-  if (!t->mproj) {
-    void *p = nullptr;
-    HIP_TRY(t->dp.get(&p, (size_t)(128 * t->n_rows + 32)));
-    t->mproj = p;
-    void *q = nullptr;
-    HIP_TRY(t->dp.get(&q, (size_t)t->n_slices + 16));
-    t->mnb = q;
-  }
-  HIP_TRY(hipMemsetAsync(t->mproj, kMargin8Zero, (size_t)(128 * t->n_rows + 32), c->stream));
-  HIP_TRY(hipMemsetAsync(t->mnb, 0, (size_t)t->n_slices + 16, c->stream));
-  void *tab = nullptr;
-  HIP_TRY(t->dp.get(&tab, 256 * 256));
-  hipLaunchKernelGGL(margin_table, dim3(256), dim3(256), 0, c->stream, mr.incl_align ? 1 : 0, (uint8_t *)tab);
-  HIP_TRY(hipGetLastError());
-  if (t->d.n_reads > 0) {
-    hipLaunchKernelGGL(pm_fill_rw, dim3((unsigned)((std::min<int64_t>((t->d.n_reads + 255) / 256, 1 << 20) + 7) & ~(int64_t)7)),
-                       dim3(256), 0, c->stream, t->d, proj_pool, mr.min_mapq, (const uint8_t *)tab,
-                       (uint8_t *)t->mproj, (uint8_t *)t->mnb, fill_dbg());
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  t->dp.put(tab);
-  t->mproj_mapq = key;
-  return GQ_OK;
-}
-
-namespace {
-
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
   const int key = 2 * min_mapq + (incl_align ? 1 : 0);  // the projection's filter and probability model
   if (t->mproj && t->mproj_mapq == key) return GQ_OK;
@@ -1305,56 +1266,21 @@ gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_map
     HIP_TRY(hipMemsetAsync(q, 0, (size_t)t->n_slices + 16, c->stream));
   }
   // the words no piece covers: biased zero terms (a rebuild for another filter rewrites only
-  // pieces); the cell fill writes every word itself
-  const int mode = margin_fill_mode();
-  const bool cells = mode == 1 || mode == 2;  // these write every word: no preset
-  if (cells) HIP_TRY(hipMemsetAsync((uint8_t *)t->mproj + 128 * t->n_rows, kMargin8Zero, 32, c->stream));
-  else HIP_TRY(hipMemsetAsync(t->mproj, kMargin8Zero, (size_t)(128 * t->n_rows + 32), c->stream));
+  // pieces)
+  HIP_TRY(hipMemsetAsync(t->mproj, kMargin8Zero, (size_t)(128 * t->n_rows + 32), c->stream));
   void *tab = nullptr;  // margin_term8 by (mapq, quality, match)
   HIP_TRY(t->dp.get(&tab, 256 * 256));
   hipLaunchKernelGGL(margin_table, dim3(256), dim3(256), 0, c->stream, incl_align ? 1 : 0, (uint8_t *)tab);
   HIP_TRY(hipGetLastError());
-  if (t->n_slices > 0) {
-    static const int fill_u = getenv("GQ_FILL_U") ? atoi(getenv("GQ_FILL_U")) : 0;  // A/B: words per lane and round
-    if (mode == 2) {  // A/B: GQ_MFILL=pieces
-      const int64_t blocks = std::min<int64_t>((t->n_slices + 3) / 4, 1 << 20);
-      hipLaunchKernelGGL(mproj_fill_pieces, dim3((unsigned)blocks), dim3(256), 0, c->stream, t->d, t->n_slices, min_mapq,
-                         (const uint8_t *)tab, (uint8_t *)t->mproj, (uint8_t *)t->mnb);
-    } else if (mode == 1) {  // A/B: GQ_MFILL=cells
-      unsigned long long *nd = nullptr;
-      int64_t *dl = nullptr;
-      HIP_TRY(t->dp.get((void **)&nd, sizeof(unsigned long long)));
-      HIP_TRY(t->dp.get((void **)&dl, sizeof(int64_t) * (size_t)t->n_slices));
-      HIP_TRY(hipMemsetAsync(nd, 0, sizeof(unsigned long long), c->stream));
-      const int64_t blocks = std::min<int64_t>((t->n_slices + 3) / 4, 1 << 20);
-      hipLaunchKernelGGL(mproj_fill_cells, dim3((unsigned)blocks), dim3(256), 0, c->stream, t->d, t->n_slices, min_mapq,
-                         (const uint8_t *)tab, (uint8_t *)t->mproj, (uint8_t *)t->mnb, dl, nd);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(mproj_fill_deep, dim3((unsigned)std::min<int64_t>(blocks, 2048)), dim3(256), 0, c->stream, t->d,
-                         (const int64_t *)dl, (const unsigned long long *)nd, min_mapq, (const uint8_t *)tab,
-                         (uint8_t *)t->mproj, (uint8_t *)t->mnb);
-      t->dp.put(nd);
-      t->dp.put(dl);
-    } else if (mode == 3 || fill_slice_major()) {  // A/B: the slice-major fill of round 4 (GQ_MFILL / GQ_FILL=slice)
-      auto kf = fill_u == 4 ? mproj_fill<4> : fill_u == 2 ? mproj_fill<2> : mproj_fill<1>;
-      hipLaunchKernelGGL(kf, dim3((unsigned)std::min<int64_t>((t->n_slices + 3) / 4, 1 << 20)), dim3(256), 0,
-                         c->stream, t->d, t->n_slices, min_mapq, (const uint8_t *)tab, (uint8_t *)t->mproj,
-                         (uint8_t *)t->mnb);
-    } else if (t->d.n_reads > 0) {
-      // mnb: set per slice by the words (a rebuild for another filter starts from zero)
-      HIP_TRY(hipMemsetAsync(t->mnb, 0, (size_t)t->n_slices + 16, c->stream));
-      static const int fill_w = getenv("GQ_FILL_W") ? atoi(getenv("GQ_FILL_W")) : 1;  // words per lane unit
-      auto kf = fill_u == 2 ? mproj_fill_rw<2, 1>
-                : fill_u == 4 ? mproj_fill_rw<4, 1>
-                : fill_w == 2 ? mproj_fill_rw<1, 2>
-                : fill_w == 4 ? mproj_fill_rw<1, 4>
-                              : mproj_fill_rw<1, 1>;
-      hipLaunchKernelGGL(kf, dim3((unsigned)((std::min<int64_t>((t->d.n_reads + 255) / 256, 1 << 20) + 7) & ~(int64_t)7)),
-                         dim3(256), 0, c->stream, t->d, min_mapq, (const uint8_t *)tab, (uint8_t *)t->mproj,
-                         (uint8_t *)t->mnb, fill_dbg());
-    }
+  if (t->n_slices > 0 && t->d.n_reads > 0) {
+    // mnb: set per slice by the words (a rebuild for another filter starts from zero)
+    HIP_TRY(hipMemsetAsync(t->mnb, 0, (size_t)t->n_slices + 16, c->stream));
+    hipLaunchKernelGGL(mproj_fill_rw,
+                       dim3((unsigned)((std::min<int64_t>((t->d.n_reads + 255) / 256, 1 << 20) + 7) & ~(int64_t)7)),
+                       dim3(256), 0, c->stream, t->d, min_mapq, (const uint8_t *)tab, (uint8_t *)t->mproj,
+                       (uint8_t *)t->mnb, fill_dbg());
+    HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   t->dp.put(tab);
   t->mproj_mapq = key;
@@ -1641,8 +1567,7 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   // projection and margin projection (A/B; the same candidates)
   static const bool som_proj = getenv("GQ_SOM") && strcmp(getenv("GQ_SOM"), "proj") == 0;
   const bool direct = !som_proj && t->d.seq_cap >= 8;
-  const MarginReq mreq{(int)p->min_mapq, true};  // (with the projection, the margin projection in the same pass)
-  gq_status st = direct ? GQ_OK : ensure_projection(c, t, &mreq);  // (derived on first use)
+  gq_status st = direct ? GQ_OK : ensure_projection(c, t);  // (derived on first use)
   if (st) return st;
   st = plan(c, t, loci, SomProjCfg::kT, pt, c->tiles, 0, 0, 0, true);
   if (st) return st;
@@ -1709,13 +1634,7 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   }
   unsigned long long rec_cap = 1 << 16, pool_cap = 1 << 20, amb_cap = 4096, deep_cap = 4096;
   Counters hc{};
-  float call_ms = 0, deep_ms = 0, front_ms = 0;
-  // GQ_CALL_SPLIT=1: the split caller (somatic_front + the back end over stored records).  Measured
-  // slower at chr1 60x/30x (front 3.9 ms + back 5.5 ms against 8.6 ms for the one kernel,
-  // profiles/r04_a5_kernel_stats.csv), so the one kernel is the default.
-  static const bool split = getenv("GQ_CALL_SPLIT") && atoi(getenv("GQ_CALL_SPLIT")) != 0;
-  // GQ_CALL_WPE=2: the one-kernel caller built for 2 waves per SIMD (no spills) instead of 3
-  static const bool wpe2 = getenv("GQ_CALL_WPE") && atoi(getenv("GQ_CALL_WPE")) == 2;
+  float call_ms = 0, deep_ms = 0;
   for (int attempt = 0; attempt < 3; ++attempt) {
     HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
     HIP_TRY(c->cplx.ensure(og.total(1) * sizeof(ComplexItem)));
@@ -1779,17 +1698,13 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
     // many generations leaves a tail of idle SIMDs behind the last ones)
     if (c->call_wg_per_cu <= 0) {
       int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, split ? (const void *)somatic_call_k<false, true>
-                                                             : wpe2 ? (const void *)somatic_call_k<false, false, 2>
-                                                                    : (const void *)somatic_call_k<false, false, 3>,
-                                                       kBlock, 0) != hipSuccess ||
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)somatic_call_k<false>, kBlock, 0) != hipSuccess ||
           nb <= 0)
         nb = 3;
       c->call_wg_per_cu = nb;
     }
-    static const int grid_env = getenv("GQ_CALL_GRID") ? atoi(getenv("GQ_CALL_GRID")) : 0;  // A/B: 0 = resident
-    const int64_t grid_cap = grid_env > 0 ? (int64_t)grid_env : (int64_t)c->call_wg_per_cu * c->n_cu;
-    const int cblocks = (int)std::min<int64_t>(std::max<int64_t>(pt.n_tiles, 1), grid_cap);
+    const int cblocks =
+        (int)std::min<int64_t>(std::max<int64_t>(pt.n_tiles, 1), (int64_t)c->call_wg_per_cu * c->n_cu);
     const DeepIO dio{(int64_t *)c->deep_list.p, deep_cap, 0, nullptr, 0, 0};
     // the candidates' records in list order (every caller kernel below reads them)
     HIP_TRY(c->cands.ensure(sizeof(CandRec) * (size_t)std::max<unsigned long long>(n_cand, 1)));
@@ -1797,64 +1712,15 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
                        (const Tile *)c->tiles.p, (const Tile *)c->tiles2.p, (const ComplexItem *)c->cplx.p, og,
                        (const Counters *)ctr, sw, t->d, n->d, (CandRec *)c->cands.p);
     HIP_TRY(hipGetLastError());
-    front_ms = 0;
-    if (!split) {
-      auto k1 = wpe2 ? somatic_call_k<false, false, 2> : somatic_call_k<false, false, 3>;
-      hipLaunchKernelGGL(k1, dim3(cblocks), dim3(kBlock), 0, c->stream, (const CandRec *)c->cands.p, t->d, n->d, *p,
-                         (SomRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, og, ctr, sw, (AmbItem *)c->amb.p,
-                         amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, rv, dbg, dio,
-                         ElemStore{});
-      HIP_TRY(hipGetLastError());
-    } else {
-      // the split caller, in batches of at most kStoreBatch candidates (the store: 5 KiB each):
-      // somatic_front (covers + element records, latency-bound, many waves) then the back end
-      // (tables, FP64 genotypes, evidence) over the stored records
-      constexpr int64_t kStoreBatch = 1 << 20;
-      const int64_t nb = std::min<int64_t>((int64_t)n_cand, kStoreBatch);
-      const size_t hdr_b = ((size_t)std::max<int64_t>(nb, 1) * sizeof(uint4) + 255) & ~(size_t)255;
-      const size_t el_b = (size_t)std::max<int64_t>(nb, 1) * 2 * kFastCap * sizeof(uint4);
-      const size_t cov_b = (size_t)std::max<int64_t>(nb, 1) * 2 * kFastCap * sizeof(int32_t);
-      HIP_TRY(c->el_store.ensure(hdr_b + el_b + cov_b));
-      if (c->front_wg_per_cu <= 0) {
-        int fb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fb, somatic_front, kBlock, 0) != hipSuccess || fb <= 0) fb = 6;
-        c->front_wg_per_cu = fb;
-      }
-      uint8_t *sb = (uint8_t *)c->el_store.p;
-      for (int64_t b0 = 0; b0 < (int64_t)n_cand; b0 += kStoreBatch) {
-        const int64_t b1 = std::min<int64_t>((int64_t)n_cand, b0 + kStoreBatch);
-        const ElemStore es{(uint4 *)sb, (uint4 *)(sb + hdr_b), (int32_t *)(sb + hdr_b + el_b), b0, b1};
-        const int64_t waves = b1 - b0;
-        const unsigned fblocks = (unsigned)std::min<int64_t>((waves + kSomWaves - 1) / kSomWaves,
-                                                            (int64_t)c->front_wg_per_cu * c->n_cu);
-        const unsigned bblocks = (unsigned)std::min<int64_t>((waves + kSomWaves - 1) / kSomWaves, grid_cap);
-        if (b0 > 0) {  // the previous batch's front time (its back end keeps the GPU busy meanwhile)
-          HIP_TRY(hipEventSynchronize(c->ev[7]));
-          float ms = 0;
-          (void)hipEventElapsedTime(&ms, c->ev[6], c->ev[7]);
-          front_ms += ms;
-        }
-        HIP_TRY(hipEventRecord(c->ev[6], c->stream));
-        hipLaunchKernelGGL(somatic_front, dim3(fblocks), dim3(kBlock), 0, c->stream, (const CandRec *)c->cands.p, t->d,
-                           n->d, *p, ctr, sw, dbg, dio, es);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev[7], c->stream));
-        hipLaunchKernelGGL((somatic_call_k<false, true>), dim3(bblocks), dim3(kBlock), 0, c->stream,
-                           (const CandRec *)c->cands.p, t->d, n->d, *p, (SomRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, og, ctr, sw,
-                           (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0,
-                           rv, dbg, dio, es);
-        HIP_TRY(hipGetLastError());
-      }
-    }
+    hipLaunchKernelGGL(somatic_call_k<false>, dim3(cblocks), dim3(kBlock), 0, c->stream, (const CandRec *)c->cands.p,
+                       t->d, n->d, *p, (SomRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, og, ctr, sw,
+                       (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, rv,
+                       dbg, dio);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     HIP_TRY(hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     (void)hipEventElapsedTime(&call_ms, c->ev[2], c->ev[3]);
-    if (split && n_cand > 0) {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, c->ev[6], c->ev[7]);
-      front_ms += ms;
-    }
     deep_ms = 0;
     bool retry = false;
     if (hc.n_deep > deep_cap) {
@@ -1870,14 +1736,13 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
       HIP_TRY(c->deep_scratch.ensure((size_t)nw * wb + 256));
       HIP_TRY(hipEventRecord(c->ev[5], c->stream));
       const unsigned blocks = (unsigned)((nw + kSomWaves - 1) / kSomWaves);
-      hipLaunchKernelGGL((somatic_call_k<true, false>), dim3(blocks), dim3(kBlock), 0, c->stream,
+      hipLaunchKernelGGL(somatic_call_k<true>, dim3(blocks), dim3(kBlock), 0, c->stream,
                          (const CandRec *)c->cands.p, t->d, n->d, *p,
                          (SomRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, og, ctr, sw,
                          (AmbItem *)(ain ? nullptr : c->amb.p), ain ? (unsigned long long)0 : amb_cap, ain, aref,
                          ain ? n_items : (int64_t)0, ain ? RefView{nullptr, nullptr} : rv, dbg,
                          DeepIO{(int64_t *)c->deep_list.p, 0, ain ? 0 : n_items, (uint8_t *)c->deep_scratch.p, scap,
-                                kMaxG, (int64_t *)c->deep_list.p + deep_cap, deep_cap},
-                         ElemStore{});
+                                kMaxG, (int64_t *)c->deep_list.p + deep_cap, deep_cap});
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(c->ev[3], c->stream));
       HIP_TRY(hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
@@ -1909,14 +1774,13 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
       const size_t wb = deep_wave_bytes(scap, maxg, kWideNS);
       HIP_TRY(c->deep_scratch.ensure((size_t)nw * wb + 256));
       HIP_TRY(hipEventRecord(c->ev[5], c->stream));
-      hipLaunchKernelGGL((somatic_call_k<true, false, 3, kWideNS>), dim3((unsigned)((nw + kSomWaves - 1) / kSomWaves)),
+      hipLaunchKernelGGL((somatic_call_k<true, kWideNS>), dim3((unsigned)((nw + kSomWaves - 1) / kSomWaves)),
                          dim3(kBlock), 0, c->stream, (const CandRec *)c->cands.p, t->d, n->d, *p, (SomRec *)c->srecs.p,
                          rec_cap, (uint8_t *)c->pool.p, pool_cap, og, ctr, sw, (AmbItem *)(ain ? nullptr : c->amb.p),
                          ain ? (unsigned long long)0 : amb_cap, ain, aref, ain ? n_ain : (int64_t)0,
                          ain ? RefView{nullptr, nullptr} : rv, dbg,
                          DeepIO{(int64_t *)c->deep_list.p + deep_cap, 0, n_items, (uint8_t *)c->deep_scratch.p,
-                                scap, maxg, nullptr, 0},
-                         ElemStore{});
+                                scap, maxg, nullptr, 0});
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(c->ev[3], c->stream));
       HIP_TRY(hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
@@ -1984,7 +1848,7 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   }
   for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
   if ((dbg & 16) && hc.prof[5])
-    fprintf(stderr, "gq somatic_call prof (cycles/candidate/wave): front|records %.0f (tumor fold %.0f) tables %.0f "
+    fprintf(stderr, "gq somatic_call prof (cycles/candidate/wave): front %.0f (tumor fold %.0f) tables %.0f "
             "tumor-genotypes %.0f normal-genotypes+evidence %.0f (%llu candidates reached)\n", (double)hc.prof[0] / hc.prof[5],
             (double)hc.prof[1] / hc.prof[5], (double)hc.prof[2] / hc.prof[5], (double)hc.prof[3] / hc.prof[5],
             (double)hc.prof[4] / hc.prof[5], hc.prof[5]);
@@ -2016,7 +1880,7 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   c->timings.deep_max = (int64_t)hc.deep_max;
   c->timings.call_ms = call_ms;
   c->timings.deep_ms = deep_ms;
-  c->timings.front_ms = front_ms;
+  c->timings.front_ms = 0;
   c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
   *out = res;
   return GQ_OK;
@@ -2209,8 +2073,7 @@ gq_status gq_germline_standard(gq_ctx *c, const gq_dev_reads *rd, const gq_loci 
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   Plan pt;
-  const MarginReq mreq{(int)p->min_mapq, false};  // (with the projection, the margin projection in the same pass)
-  gq_status st = ensure_projection(c, rd, &mreq);  // (derived on first use)
+  gq_status st = ensure_projection(c, rd);  // (derived on first use)
   if (st) return st;
   st = plan(c, rd, loci, SomProjCfg::kT, pt, c->tiles, 0, 0, 0, true);
   if (st) return st;

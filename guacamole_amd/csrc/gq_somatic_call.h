@@ -811,28 +811,15 @@ __device__ __forceinline__ bool call_front(const CandRec &cr, int64_t it, const 
   return true;
 }
 
-// The element store between the split caller's kernels (somatic_front -> somatic_call_k<false,
-// true>), for the candidates [b0, b1) of the list: per candidate a header {nc tumor, nc normal,
-// reference-base mask tumor, normal} (nc tumor = kElSkip: the front listed it for the deep
-// kernel) and kFastCap element records and covering-read offsets per sample.
-constexpr uint32_t kElSkip = 0xFFFFFFFFu;
-struct ElemStore {
-  uint4 *hdr;
-  uint4 *el;
-  int32_t *cov;
-  int64_t b0, b1;
-};
-
-// WPE: waves per SIMD the fast kernel's register budget must allow (3: 168 VGPRs and some
-// spills; 2: no spills; GQ_CALL_WPE picks, see gq_somatic_standard).  The deep kernel: 2.
-template <bool DEEP, bool BACK = false, int WPE = 3, int NSD = kSlots>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2 : WPE))) void somatic_call_k(
+// The fast kernel's register budget allows 3 waves per SIMD (168 VGPRs and some spills), the
+// deep kernel's 2.
+template <bool DEEP, int NSD = kSlots>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2 : 3))) void somatic_call_k(
     const CandRec *__restrict__ cands, DevReads RT, DevReads RN, gq_somatic_params prm, SomRec *__restrict__ recs,
     unsigned long long rec_cap,
     uint8_t *__restrict__ pool, unsigned long long pool_cap, OutGeom og, Counters *ctr, SomWin sw,
     AmbItem *__restrict__ amb_out, unsigned long long amb_cap, const AmbItem *__restrict__ amb_in,
-    const uint8_t *__restrict__ amb_ref, int64_t n_amb_in, RefView ref, int dbg, DeepIO dio, ElemStore es) {
-  // BACK: the candidates [es.b0, es.b1) whose covers and element records somatic_front stored.
+    const uint8_t *__restrict__ amb_ref, int64_t n_amb_in, RefView ref, int dbg, DeepIO dio) {
   // amb_in == nullptr: the candidates (fast kernel) or the deep list (deep kernel); loci where a
   // sample's MD-derived reference bases disagree are listed (amb_out) for the heap-order replay.
   // amb_in != nullptr (deep kernel only): the listed loci with both samples' bases resolved
@@ -871,19 +858,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2
     m.cap = kFastCap;
     m.maxG = kMaxG;
   }
-  static_assert(!(DEEP && BACK), "the deep kernel runs its own front");
   // amb_sel: a heap-order replay over the amb_in positions listed in dio.list (the wide kernel
   // over the replayed loci the deep kernel's table could not hold), not over all of amb_in
   const bool amb_sel = DEEP && amb_in != nullptr && dio.n_in > 0;
   const unsigned long long n_items = amb_sel  ? (unsigned long long)dio.n_in
                                      : amb_in ? (unsigned long long)n_amb_in
                                      : DEEP ? (unsigned long long)dio.n_in
-                                     : BACK ? (unsigned long long)es.b1
                                             : ctr->part_off[1][kParts];
-  const int64_t li0 = BACK ? es.b0 + gwave : gwave;
-  // dbg & 16: phase clocks per candidate and wave (front or the stored records' load, -, tables,
-  // tumor genotypes, normal genotypes + evidence + record, candidates), summed per workgroup in LDS (a global
-  // atomic per phase would queue every wave on one address) and added to ctr->prof at the end
+  // dbg & 16: phase clocks per candidate and wave (front, -, tables, tumor genotypes, normal
+  // genotypes + evidence + record, candidates), summed per workgroup in LDS (a global atomic
+  // per phase would queue every wave on one address) and added to ctr->prof at the end
   __shared__ unsigned long long s_clk[6];
   __shared__ double s_succ[256];
   if (threadIdx.x < 6) s_clk[threadIdx.x] = 0;
@@ -907,8 +891,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2
   };
   int64_t it_next = 0, la_next = 0;
   CandRec item_next{};
-  if (li0 < (int64_t)n_items) item_next = fetch_item(li0, it_next, la_next);
-  for (int64_t li = li0; li < (int64_t)n_items; li += nwaves_total) {
+  if (gwave < (int64_t)n_items) item_next = fetch_item(gwave, it_next, la_next);
+  for (int64_t li = gwave; li < (int64_t)n_items; li += nwaves_total) {
     tick(-1);
     if ((dbg & 16) && lane == 0) atomicAdd(&s_clk[5], 1ull);
     const int64_t it = it_next, la = la_next;
@@ -919,27 +903,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2
     const int64_t t_ord0 = item.ord0;
     const int64_t rb[2] = {item.rb[0], item.rb[1]};
     uint32_t nc[2], mask[2];
-    if constexpr (BACK) {
-      // the front's records -> LDS (the tables, folds and evidence read them across lanes)
-      const uint4 h = es.hdr[li - es.b0];
-      if (h.x == kElSkip) continue;
-      nc[0] = h.x;
-      nc[1] = h.y;
-      mask[0] = h.z;
-      mask[1] = h.w;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const size_t o = ((size_t)(li - es.b0) * 2 + s) * kFastCap;
-        for (uint32_t k = lane; k < nc[s]; k += 64) {
-          m.el[s][k] = es.el[o + k];
-          m.cov[s][k] = es.cov[o + k];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    } else {
-      if (!call_front<DEEP>(item, it, RT, RN, prm, ctr, sw, m, dbg, dio, nc, mask)) continue;
-    }
+    if (!call_front<DEEP>(item, it, RT, RN, prm, ctr, sw, m, dbg, dio, nc, mask)) continue;
     Pile<NS> PS[2];
     const int fb = ref.b ? (int)ref.b[ref.off[t_contig] + pos] : -1;
 #pragma unroll
@@ -1191,53 +1155,5 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 2
   if (dbg & 16) {
     __syncthreads();
     if (threadIdx.x < 6 && s_clk[threadIdx.x]) atomicAdd(&ctr->prof[threadIdx.x], s_clk[threadIdx.x]);
-  }
-}
-
-// The split caller's front (GQ_CALL_SPLIT=1; off by default, see gq_somatic_standard): covers
-// and element records of the candidates [es.b0, es.b1) into the element store, one wave per
-// candidate.  It holds only the front's registers (4 waves per SIMD against the one kernel's 3);
-// measured, that did not pay for the store's traffic and the second pass over the candidates.
-#ifndef GQ_FRONT_WPE
-#define GQ_FRONT_WPE 4
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GQ_FRONT_WPE))) void somatic_front(
-    const CandRec *__restrict__ cands, DevReads RT, DevReads RN, gq_somatic_params prm, Counters *ctr, SomWin sw,
-    int dbg, DeepIO dio, ElemStore es) {
-  constexpr int FW = kSomWaves;
-  __shared__ int32_t s_cov[FW][2][kFastCap];
-  __shared__ uint32_t s_tmp[FW][2 * kFastCap];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  // (wave-uniform, and known to be: the candidate records then load into scalar registers)
-  const int64_t gwave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t nwaves_total = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  CallMem m{};
-  m.cov[0] = s_cov[wv][0];
-  m.cov[1] = s_cov[wv][1];
-  m.tmp = s_tmp[wv];
-  m.cap = kFastCap;
-  m.maxG = kMaxG;
-  CandRec item_next{};
-  if (es.b0 + gwave < es.b1) item_next = cands[es.b0 + gwave];
-  for (int64_t li = es.b0 + gwave; li < es.b1; li += nwaves_total) {
-    const CandRec item = item_next;
-    if (li + nwaves_total < es.b1) item_next = cands[li + nwaves_total];
-    const size_t o = (size_t)(li - es.b0) * 2 * kFastCap;
-    m.el[0] = es.el + o;  // the element records go straight to the store
-    m.el[1] = es.el + o + kFastCap;
-    uint32_t nc[2], mask[2];
-    const bool go = call_front<false>(item, li, RT, RN, prm, ctr, sw, m, dbg, dio, nc, mask);
-    uint4 h = make_uint4(kElSkip, 0, 0, 0);
-    if (go) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        for (int d = 1; d < 64; d <<= 1) mask[s] |= __shfl_xor(mask[s], d, 64);
-        for (uint32_t k = lane; k < nc[s]; k += 64) es.cov[o + (size_t)s * kFastCap + k] = m.cov[s][k];
-      }
-      h = make_uint4(nc[0], nc[1], mask[0], mask[1]);
-    }
-    if (lane == 0) es.hdr[li - es.b0] = h;
-    __builtin_amdgcn_wave_barrier();  // (the next candidate rewrites this wave's LDS)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   }
 }

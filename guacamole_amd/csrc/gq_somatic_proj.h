@@ -1,5 +1,5 @@
 // gq_somatic_proj.h — somatic candidate loci over the read projections (somatic_proj), and
-// the tumor's margin projection it reads (mproj_fill).  Included inside gq_somatic.hip's
+// the tumor's margin projection it reads (mproj_fill_rw).  Included inside gq_somatic.hip's
 // anonymous namespace.
 //
 // somatic_proj restates somatic_tile's per-locus test (SomaticStandardCaller.scala:184-206: the
@@ -51,52 +51,6 @@ __global__ void margin_table(int incl_align, uint8_t *__restrict__ tab) {
 }
 
 typedef uint64_t gq_u64m __attribute__((aligned(1)));  // unaligned 8-byte loads (gfx950 global memory)
-
-// Piece setup of the margin fill: the read's descriptor and its MD events at the piece's loci as
-// a bit mask (MD offsets are reference offsets from the read's start, sorted).  Reads the mapq
-// filter drops (QualityAlignedReadsFilter, PileupElementsFilter.scala:25-36) are skipped: their
-// loci keep the pool's kMargin8Zero fill.
-__device__ __forceinline__ bool margin_setup(const DevReads &R, int min_mapq, int64_t md_off, PieceMeta &m) {
-  if (min_mapq > 0 && (int)m.mq < min_mapq) return false;
-  const int32_t nmd = (int32_t)(m.info & 0xFFFFu);
-  const uint32_t *ev = R.md_ev + md_off;
-  const int32_t o0 = 8 * m.s0 - m.s;  // offset of the piece's first locus
-  uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;  // (registers: a dynamic index would go to scratch)
-  auto mark = [&](uint32_t v) {
-    const int32_t i = (int32_t)(v >> 8) - o0;
-    if (i < 0 || i >= 128) return;
-    const uint32_t bit = 1u << (i & 31);
-    e0 |= (i >> 5) == 0 ? bit : 0u;
-    e1 |= (i >> 5) == 1 ? bit : 0u;
-    e2 |= (i >> 5) == 2 ? bit : 0u;
-    e3 |= (i >> 5) == 3 ? bit : 0u;
-  };
-  if (nmd <= 4) {  // the common read: its (few) events in one round of loads
-    uint32_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = k < nmd ? ev[k] : 0xFFFFFFFFu;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < nmd) mark(v[k]);
-  } else {  // the first event at or past the piece's first locus, then the piece's events
-    int k = 0, hi = nmd;
-    while (k < hi) {
-      const int mid = (k + hi) >> 1;
-      if ((int32_t)(ev[mid] >> 8) < o0) k = mid + 1;
-      else hi = mid;
-    }
-    for (; k < nmd; ++k) {
-      const uint32_t v = ev[k];
-      if ((int32_t)(v >> 8) - o0 >= 128) break;
-      mark(v);
-    }
-  }
-  m.ev[0] = e0;
-  m.ev[1] = e1;
-  m.ev[2] = e2;
-  m.ev[3] = e3;
-  return true;
-}
 
 // The margin word (8 loci, a byte each; hom_ref_margin_lane's terms in 1/8 units, biased) of read
 // r at column col, from its piece m.  Loci outside the read's Match/Mismatch blocks hold
@@ -185,53 +139,6 @@ __device__ __forceinline__ MarginRaw margin_fetch(const DevReads &R, int64_t r, 
   return x;
 }
 
-// The margin projection of the tumor reads, laid out as `proj` (a byte per projection nibble:
-// word w of the row pool at mproj + 8 w), one wave per slice, a lane per word (the rows row_count
-// assigned, stored); mnb marks slices holding a kMargin8None term.
-template <int KU>
-__global__ __launch_bounds__(256) void mproj_fill(DevReads R, int64_t n_slices, int min_mapq,
-                                                  const uint8_t *__restrict__ tab, uint8_t *__restrict__ mproj,
-                                                  uint8_t *__restrict__ mnb) {
-  __shared__ PieceMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][KU * 64];
-  __shared__ uint32_t s_row[4][64];  // the table row of the slice's first read's mapq (256 bytes)
-  PieceMeta *meta = s_meta[threadIdx.x >> 6];
-  uint32_t *owner = s_owner[threadIdx.x >> 6];
-  uint32_t *row = s_row[threadIdx.x >> 6];
-  const uint8_t *lrow = reinterpret_cast<const uint8_t *>(row);
-  const int lane = threadIdx.x & 63;
-  const int64_t w0 = wave_id();
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t slot = w0; slot < n_slices; slot += nw) {
-    if (R.pbad[slot]) continue;  // uniform
-    uint2 *out = reinterpret_cast<uint2 *>(mproj) + 16 * R.srow[slot];  // the slice's block rows
-    const SliceWin W = slice_stored(R, slot);
-    // most reads share one mapping quality: its table row in LDS saves the words' lookups a
-    // round trip to the cache hierarchy
-    const uint32_t lmq = W.rz > W.ra ? (uint32_t)R.mapq[W.ra] : 0u;
-    row[lane] = reinterpret_cast<const uint32_t *>(tab + (lmq << 8))[lane];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    bool none = false;
-    slice_fill<true, KU>(
-        R, W, R.prow + R.soff[slot], meta, owner,
-        [&](int64_t, PieceMeta &m, int64_t mdo) { return margin_setup(R, min_mapq, mdo, m); },
-        [&](int64_t r, const PieceMeta &m, int32_t col, uint32_t evb) { return margin_fetch(R, r, m, col, evb, tab); },
-        [&](bool act, const MarginRaw &x, int64_t, const PieceMeta &m, int32_t col, uint32_t evb) {
-          if (act) {
-            const uint2 w = x.gen ? x.word : margin_terms8(m, x.q, x.valid, evb, tab, lrow, lmq);
-            out[16 * (int64_t)m.row + (col & 15)] = w;
-            auto has = [](uint32_t v) {  // a zero byte
-              return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u;
-            };
-            none = none || has(w.x) || has(w.y);
-          }
-        });
-    const bool any = __ballot(none) != 0;
-    if ((threadIdx.x & 63) == 0) mnb[slot] = any ? 1 : 0;
-  }
-}
-
 // The MD-event bits of read m's word at column col (bit k: locus 8 col + k): v holds up to four
 // events loaded by the fetch (0xFFFFFFFF: none); a read with more has them in evb already.
 __device__ __forceinline__ uint32_t word_event_bits(const ReadMeta &m, int32_t col, const uint32_t (&v)[4], uint32_t evb) {
@@ -249,8 +156,7 @@ struct MarginRW {
   uint32_t evb;
 };
 __device__ __forceinline__ MarginRW margin_fetch_rw(const DevReads &R, int64_t r, const ReadMeta &m, int32_t col,
-                                                    const uint8_t *__restrict__ tab, uint64_t pre = 0,
-                                                    bool fast = false) {
+                                                    const uint8_t *__restrict__ tab, uint64_t pre, bool fast) {
   MarginRW o;
   const int32_t nmd = (int32_t)(m.info & 0xFFFFu);
   const uint32_t *ev = R.md_ev + m.md_off;
@@ -293,19 +199,18 @@ __device__ __forceinline__ MarginRW margin_fetch_rw(const DevReads &R, int64_t r
 
 // The margin projection, read-major (read_fill): a wave per 64 consecutive reads, a lane per
 // word; mnb (zeroed by the caller) gets 1 on each slice holding a kMargin8None term.
-template <int KU, int KW>
 __global__ __launch_bounds__(256) void mproj_fill_rw(DevReads R, int min_mapq, const uint8_t *__restrict__ tab,
                                                      uint8_t *__restrict__ mproj, uint8_t *__restrict__ mnb, int dbg) {
   constexpr int kRows = 4;  // table rows staged per batch: its first kRows distinct mapping qualities
   __shared__ ReadMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][KU * 64];
+  __shared__ uint32_t s_owner[4][64];
   __shared__ uint32_t s_row[4][kRows * 64];
   uint32_t *row = s_row[threadIdx.x >> 6];
   const uint8_t *lrow = reinterpret_cast<const uint8_t *>(row);
   const int lane = threadIdx.x & 63;
   uint32_t lmq[kRows];  // (wave-uniform) the staged rows' mapping qualities; 0xFFFFFFFF: none
   uint2 *out = reinterpret_cast<uint2 *>(mproj);
-  read_fill<KU, true, KW>(
+  read_fill(
       R, s_meta[threadIdx.x >> 6], s_owner[threadIdx.x >> 6], dbg, R.qual,
       [&](int64_t r0) {
         // a few mapping qualities cover a batch's reads (most share one): their table rows in LDS,
@@ -346,373 +251,6 @@ __global__ __launch_bounds__(256) void mproj_fill_rw(DevReads R, int min_mapq, c
                                     : margin_terms8(piece_meta(m), o.x.q, o.x.valid, evb, tab, k < 0 ? nullptr : lr,
                                                     m.mq);
           out[16 * grow + (col & 15)] = w;
-          auto has = [](uint32_t v) {  // a zero byte
-            return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u;
-          };
-          if (has(w.x) || has(w.y)) mnb[slot] = 1;
-        }
-      });
-}
-
-// ---- The margin projection by pieces (piece_fill in gq_host.h; A/B: GQ_FILL=pieces) ----
-struct MarginCell {
-  uint64_t q;       // the word's qualities (loci outside the read zero)
-  uint32_t valid;   // byte mask of its loci inside the read (0: a read the mapq filter drops)
-  uint16_t evb;     // its loci holding an MD event
-  uint16_t mq;      // the read's mapping quality (its table row)
-};
-// The MD-event bits of read r's word at column col (bit k: locus 8 col + k), from its events.
-__device__ __forceinline__ uint32_t word_events(const DevReads &R, int64_t md_off, uint32_t info, int32_t s,
-                                                int32_t col) {
-  const int32_t nmd = (int32_t)(info & 0xFFFFu);
-  const uint32_t *ev = R.md_ev + md_off;
-  const int32_t i0 = 8 * col - s;
-  int k = 0, hi = nmd;
-  while (k < hi) {
-    const int mid = (k + hi) >> 1;
-    if ((int32_t)(ev[mid] >> 8) < i0) k = mid + 1;
-    else hi = mid;
-  }
-  uint32_t evb = 0;
-  for (; k < nmd; ++k) {
-    const int32_t i = (int32_t)(ev[k] >> 8) - i0;
-    if (i >= 8) break;
-    evb |= 1u << i;
-  }
-  return evb;
-}
-
-// ---- The margin projection by cells (the default; the projection's proj_fill_cells design) ----
-// A wave per slice, a lane per cell: 32-byte window records in LDS (pool offset,
-// [start, end), ColDesc info, mapping quality, up to four MD-event offsets), a u8 map cell ->
-// window read, then per cell one 8-byte load of its qualities and eight table lookups in the
-// LDS row of the wave's common mapping quality.  Every word written (kMargin8Zero where no kept
-// element lies), 64 consecutive words per store; mnb[slot] = 1 where a word holds kMargin8None.
-struct __attribute__((aligned(16))) MCellRec {
-  uint32_t a;         // seq_off + leading clip - seq_off[window's first read]
-  int32_t s, e;       // [start, end)
-  uint32_t info;      // ColDesc info
-  uint32_t mq;        // mapping quality; bit 8: dropped by the mapq filter; bit 9: events not below
-  uint32_t ev01, ev23;  // up to four MD-event offsets from s, 16 bits each (0xFFFF: none)
-  uint32_t pad;
-};
-__global__ __launch_bounds__(256) void mproj_fill_cells(DevReads R, int64_t n_slices, int min_mapq,
-                                                        const uint8_t *__restrict__ tab, uint8_t *__restrict__ mproj,
-                                                        uint8_t *__restrict__ mnb, int64_t *__restrict__ deep,
-                                                        unsigned long long *__restrict__ n_deep) {
-  constexpr int kWin = 255, kRows = 64;
-  __shared__ MCellRec s_rec[4][kWin];
-  __shared__ uint8_t s_map[4][kRows * 16];
-  __shared__ uint32_t s_row[4][64];  // the table row of one mapping quality (256 bytes)
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  MCellRec *rec = s_rec[wv];
-  uint8_t *map = s_map[wv];
-  const uint8_t *lrow = reinterpret_cast<const uint8_t *>(s_row[wv]);
-  uint32_t lmq = 0;  // most reads share one mapping quality: its row (the wave's first slice's first read)
-  {
-    const int64_t slot = wave_id();
-    if (slot < n_slices) {
-      const int64_t ra = R.sra[slot];
-      lmq = ra < R.n_reads ? (uint32_t)R.mapq[ra] : 0u;
-    }
-    s_row[wv][lane] = reinterpret_cast<const uint32_t *>(tab + (lmq << 8))[lane];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  }
-  const uint2 zero = make_uint2(0x80808080u, 0x80808080u);
-  auto has_none = [](uint2 w) {  // a kMargin8None (zero) byte
-    auto z = [](uint32_t v) { return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u; };
-    return z(w.x) || z(w.y);
-  };
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t slot = wave_id(); slot < n_slices; slot += nw) {
-    const int64_t g0 = R.srow[slot];
-    const int32_t nr = (int32_t)(R.srow[slot + 1] - g0);
-    if (nr <= 0) continue;
-    uint2 *out = reinterpret_cast<uint2 *>(mproj) + 16 * g0;
-    const SliceWin W = slice_stored(R, slot);
-    const int32_t nwin = (int32_t)(W.rz - W.ra);
-    if (R.pbad[slot] || nwin > kWin || nwin <= 0) {
-      for (int32_t c = lane; c < 16 * nr; c += 64) out[c] = zero;
-      if (!R.pbad[slot] && nwin > kWin && lane == 0) deep[atomicAdd(n_deep, 1ull)] = slot;
-      continue;
-    }
-    const int64_t base = R.seq_off[W.ra];
-    const uint8_t *pool = R.qual + base;
-    const int64_t span = R.seq_cap - base;
-    const uint16_t *prw = R.prow + R.soff[slot];
-    for (int32_t i = lane; i < nwin; i += 64) {
-      const int64_t r = W.ra + i;
-      const ColDesc d = R.cdesc[r];
-      const int32_t ld = R.lead[r];
-      const int64_t so = R.seq_off[r];
-      const uint32_t mq = R.mapq[r];
-      const int64_t mo = R.md_off[r];
-      const int64_t av = so + (ld > 0 ? ld : 0) - base;  // (off the window's byte run: the slow path)
-      MCellRec m;
-      m.a = R.pool_ordered && av >= 0 && av < (int64_t)kCell3Far ? (uint32_t)av : kCell3Far;
-      m.s = d.start;
-      m.e = d.end;
-      m.info = d.info;
-      m.mq = mq | (min_mapq > 0 && (int)mq < min_mapq ? 0x100u : 0u);
-      const int32_t nmd = (int32_t)(d.info & 0xFFFFu);
-      uint32_t v[4];
-      bool in = nmd <= 4;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        v[q] = q < nmd && in ? R.md_ev[mo + q] >> 8 : 0xFFFFu;
-        in = in && v[q] <= 0xFFFFu && (q >= nmd || v[q] < 0xFFFFu);
-      }
-      m.ev01 = (v[0] & 0xFFFFu) | (v[1] << 16);
-      m.ev23 = (v[2] & 0xFFFFu) | (v[3] << 16);
-      if (!in) m.mq |= 0x200u;
-      m.pad = 0;
-      rec[i] = m;
-    }
-    bool none = false;
-    for (int32_t k0 = 0; k0 < nr; k0 += kRows) {
-      const int32_t nk = nr - k0 < kRows ? nr - k0 : kRows;
-      for (int32_t c = lane; c < 16 * nk; c += 64) map[c] = 0xFFu;
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      for (int32_t i = lane; i < nwin; i += 64) {
-        const int32_t row = prw[i];
-        int32_t s0, sl;
-        piece_of(R.prec[W.ra + i], W.qc0, s0, sl);
-        if (row == 0xFFFF || sl <= 0 || row < k0 || row >= k0 + nk) continue;
-        uint8_t *mp = map + 16 * (row - k0) + (s0 - W.qc0);
-        for (int32_t j = 0; j < sl; ++j) mp[j] = (uint8_t)i;
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      uint2 *o = out + 16 * k0;
-      for (int32_t c00 = 0; c00 < 16 * nk; c00 += 256) {  // four cells per lane, their loads together
-        uint64_t q[4];
-        uint32_t valid[4], evb[4], mqs[4];
-        uint32_t slow = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int32_t c = c00 + 64 * u + lane;
-          const uint32_t p = c < 16 * nk ? map[c] : 0xFFu;
-          q[u] = 0;
-          valid[u] = 0;
-          evb[u] = 0;
-          mqs[u] = lmq;
-          if (p == 0xFFu) continue;
-          const MCellRec m = rec[p];
-          if (m.mq & 0x100u) continue;  // dropped by the mapq filter: no element
-          const int32_t lb = 8 * (W.qc0 + (c & 15));
-          const int64_t v = (int64_t)m.a + lb - m.s;
-          if (!(m.info & kColEligible) || (m.mq & 0x200u) || m.a == kCell3Far || v < 0 || v + 8 > span) {
-            slow |= 1u << u;
-            continue;
-          }
-          const int32_t lo = min(max(m.s - lb, 0), 8), hi = min(max(m.e - lb, 0), 8);
-          q[u] = *reinterpret_cast<const gq_u64m *>(pool + (uint32_t)v);
-          if (lo > 0 || hi < 8) q[u] &= edge_mask(lo, hi);
-          valid[u] = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-          const int32_t i0 = lb - m.s;
-          uint32_t eb = 0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const uint32_t off = ((k < 2 ? m.ev01 : m.ev23) >> (16 * (k & 1))) & 0xFFFFu;
-            const uint32_t ii = (uint32_t)((int32_t)off - i0);
-            eb |= (off != 0xFFFFu && ii < 8u) ? 1u << ii : 0u;
-          }
-          evb[u] = eb;
-          mqs[u] = m.mq & 0xFFu;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int32_t c = c00 + 64 * u + lane;
-          if (c >= 16 * nk || ((slow >> u) & 1u)) continue;
-          uint2 w = zero;
-          if (valid[u])
-            w = mqs[u] == lmq ? margin_terms8_lds(q[u], valid[u], evb[u], lrow)
-                              : margin_terms8_lds(q[u], valid[u], evb[u], tab + (mqs[u] << 8));
-          o[c] = w;
-          none = none || has_none(w);
-        }
-        if (slow) {  // rare: a general CIGAR, more than four MD events, a word at the pool's end
-#pragma unroll 1
-          for (int u = 0; u < 4; ++u) {
-            if (!((slow >> u) & 1u)) continue;
-            const int32_t c = c00 + 64 * u + lane;
-            const uint32_t p = map[c];
-            const MCellRec m = rec[p];
-            const int64_t r = W.ra + p;
-            const int32_t ld = R.lead[r];
-            PieceMeta pm;
-            pm.p0 = R.seq_off[r] + (ld > 0 ? ld : 0) - m.s;  // (from the read itself: any pool order)
-            pm.s = m.s;
-            pm.e = m.e;
-            pm.s0 = 0;
-            pm.row = 0;
-            pm.info = m.info;
-            pm.mq = m.mq & 0xFFu;
-            const int32_t col = W.qc0 + (c & 15);
-            const uint32_t eb = word_events(R, R.md_off[r], m.info, m.s, col);
-            const MarginRaw x = margin_fetch(R, r, pm, col, eb, tab);
-            const uint2 w = x.gen ? x.word : margin_terms8(pm, x.q, x.valid, eb, tab);
-            o[c] = w;
-            none = none || has_none(w);
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();  // (the next chunk rewrites the map)
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    const bool any = __ballot(none) != 0;
-    if (lane == 0) mnb[slot] = any ? 1 : 0;
-  }
-}
-
-// The listed (deep) slices' margin words, slice-major (their rows preset to kMargin8Zero by
-// mproj_fill_cells).
-__global__ __launch_bounds__(256) void mproj_fill_deep(DevReads R, const int64_t *__restrict__ deep,
-                                                       const unsigned long long *__restrict__ n_deep, int min_mapq,
-                                                       const uint8_t *__restrict__ tab, uint8_t *__restrict__ mproj,
-                                                       uint8_t *__restrict__ mnb) {
-  __shared__ PieceMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][64];
-  PieceMeta *meta = s_meta[threadIdx.x >> 6];
-  uint32_t *owner = s_owner[threadIdx.x >> 6];
-  const int64_t nd = (int64_t)*n_deep;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t i = wave_id(); i < nd; i += nw) {
-    const int64_t slot = deep[i];
-    uint2 *out = reinterpret_cast<uint2 *>(mproj) + 16 * R.srow[slot];
-    bool none = false;
-    slice_fill<true, 1>(
-        R, slice_stored(R, slot), R.prow + R.soff[slot], meta, owner,
-        [&](int64_t, PieceMeta &m, int64_t mdo) { return margin_setup(R, min_mapq, mdo, m); },
-        [&](int64_t r, const PieceMeta &m, int32_t col, uint32_t evb) { return margin_fetch(R, r, m, col, evb, tab); },
-        [&](bool act, const MarginRaw &x, int64_t, const PieceMeta &m, int32_t col, uint32_t evb) {
-          if (act) {
-            const uint2 w = x.gen ? x.word : margin_terms8(m, x.q, x.valid, evb, tab);
-            out[16 * (int64_t)m.row + (col & 15)] = w;
-            auto has = [](uint32_t v) { return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u; };
-            none = none || has(w.x) || has(w.y);
-          }
-        });
-    const bool any = __ballot(none) != 0;
-    if ((threadIdx.x & 63) == 0) mnb[slot] = any ? 1 : 0;
-  }
-}
-
-// The tumor's margin projection (a biased byte per locus-read, 128 B per row) slice by slice
-// (piece_fill in gq_host.h): a wave per slice, a lane per piece, the rows built in LDS and written
-// whole (kMargin8Zero where no element of a kept read lies: no preset).  mnb[slot] = 1 where a
-// word holds a kMargin8None term.
-__global__ __launch_bounds__(256) void mproj_fill_pieces(DevReads R, int64_t n_slices, int min_mapq,
-                                                         const uint8_t *__restrict__ tab, uint8_t *__restrict__ mproj,
-                                                         uint8_t *__restrict__ mnb) {
-  __shared__ uint2 s_rows[4][kPieceRows * kPieceStride];
-  __shared__ uint32_t s_row[4][64];  // the table row of one mapping quality (256 bytes)
-  const int wv = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const uint8_t *lrow = reinterpret_cast<const uint8_t *>(s_row[wv]);
-  uint32_t lmq = 0;  // most reads share one mapping quality: its row (the wave's first slice's first read)
-  {
-    const int64_t slot = wave_id();
-    if (slot < n_slices) {
-      const int64_t ra = R.sra[slot];
-      lmq = ra < R.n_reads ? (uint32_t)R.mapq[ra] : 0u;
-    }
-    s_row[wv][lane] = reinterpret_cast<const uint32_t *>(tab + (lmq << 8))[lane];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  }
-  const uint2 zero = make_uint2(0x80808080u, 0x80808080u);
-  piece_fill<uint2, MarginCell, true>(
-      R, n_slices, s_rows[wv], reinterpret_cast<uint2 *>(mproj), zero,
-      [&](const PieceRec &m) { return !(min_mapq > 0 && (int)m.mq < min_mapq); },
-      [&](const PieceRec &m, int32_t col, MarginCell &x) {
-        const int32_t nmd = (int32_t)(m.info & 0xFFFFu);
-        if (!(m.info & kColEligible) || nmd > 4) return false;
-        const int32_t lb = 8 * col;
-        const int64_t a = m.p0 + lb;
-        if (a < 0 || a + 8 > R.seq_cap) return false;
-        const int32_t lo = min(max(m.s - lb, 0), 8), hi = min(max(m.e - lb, 0), 8);
-        x.q = *reinterpret_cast<const gq_u64m *>(R.qual + a) & edge_mask(lo, hi);
-        x.valid = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-        const int32_t i0 = lb - m.s;
-        uint32_t evb = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {  // (the piece's events came with its record)
-          const uint32_t i = (uint32_t)((int32_t)(m.ev[k] >> 8) - i0);
-          evb |= (m.ev[k] != 0xFFFFFFFFu && i < 8u) ? 1u << i : 0u;
-        }
-        x.evb = (uint16_t)evb;
-        x.mq = (uint16_t)m.mq;
-        return true;
-      },
-      [&](const PieceRec &, int32_t, const MarginCell &x) {  // terms from the LDS row or the mapq's global row
-        return x.mq == lmq ? margin_terms8_lds(x.q, x.valid, x.evb, lrow)
-                           : margin_terms8_lds(x.q, x.valid, x.evb, tab + ((uint32_t)x.mq << 8));
-      },
-      [&](const PieceRec &m, int64_t r, int32_t col) {
-        const PieceMeta pm = piece_rec_meta(m);
-        const uint32_t evb = word_events(R, m.md_off, m.info, m.s, col);
-        const MarginRaw x = margin_fetch(R, r, pm, col, evb, tab);
-        return x.gen ? x.word : margin_terms8(pm, x.q, x.valid, evb, tab);
-      },
-      [](uint2 w) {  // a kMargin8None (zero) byte
-        auto z = [](uint32_t v) { return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u; };
-        return z(w.x) || z(w.y);
-      },
-      [&](int64_t slot, bool none) {
-        if (lane == 0) mnb[slot] = none ? 1 : 0;
-      });
-}
-
-// The projection and the margin projection of one read set in one read-major pass (the
-// projection derived for a caller that also reads the margin projection): one batch setup per 64
-// reads, each word's bases and qualities loaded together; margin words only for reads the mapq
-// filter keeps (the others keep the pool's kMargin8Zero fill).
-struct PmRaw {
-  ProjRaw p;
-  MarginRW m;
-};
-__global__ __launch_bounds__(256) void pm_fill_rw(DevReads R, uint8_t *__restrict__ proj, int min_mapq,
-                                                  const uint8_t *__restrict__ tab, uint8_t *__restrict__ mproj,
-                                                  uint8_t *__restrict__ mnb, int dbg) {
-  __shared__ ReadMeta s_meta[4][64];
-  __shared__ uint32_t s_owner[4][64];
-  __shared__ uint32_t s_row[4][64];  // the table row of the batch's first read's mapq (256 bytes)
-  uint32_t *row = s_row[threadIdx.x >> 6];
-  const uint8_t *lrow = reinterpret_cast<const uint8_t *>(row);
-  const int lane = threadIdx.x & 63;
-  uint32_t lmq = 0;
-  uint32_t *pout = reinterpret_cast<uint32_t *>(proj);
-  uint2 *mout = reinterpret_cast<uint2 *>(mproj);
-  auto kept = [=](const ReadMeta &m) { return !(min_mapq > 0 && (int)m.mq < min_mapq); };
-  read_fill<1, true, 1>(
-      R, s_meta[threadIdx.x >> 6], s_owner[threadIdx.x >> 6], dbg, nullptr,
-      [&](int64_t r0) {
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        lmq = (uint32_t)R.mapq[r0];
-        row[lane] = reinterpret_cast<const uint32_t *>(tab + (lmq << 8))[lane];
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      },
-      [](const ReadMeta &) { return true; },
-      [&](int64_t r, const ReadMeta &m, int32_t col, uint64_t, bool) {
-        return PmRaw{proj_fetch(R, r, piece_meta(m), col), margin_fetch_rw(R, r, m, col, tab)};
-      },
-      [&](bool act, const PmRaw &o, int64_t, const ReadMeta &m, int32_t col, int64_t grow, int64_t slot) {
-        if (act)
-          pout[16 * grow + (col & 15)] =
-              o.p.gen ? o.p.word : proj_codes4((uint32_t)o.p.b) | (proj_codes4((uint32_t)(o.p.b >> 32)) << 4);
-        const bool mact = act && kept(m);
-        const bool all_lds = __ballot(mact && !o.m.x.gen && m.mq != lmq) == 0;  // uniform
-        if (mact) {
-          const uint32_t evb = word_event_bits(m, col, o.m.v, o.m.evb);
-          const uint2 w = o.m.x.gen ? o.m.x.word
-                          : all_lds ? margin_terms8_lds(o.m.x.q, o.m.x.valid, evb, lrow)
-                                    : margin_terms8(piece_meta(m), o.m.x.q, o.m.x.valid, evb, tab, lrow, lmq);
-          mout[16 * grow + (col & 15)] = w;
           auto has = [](uint32_t v) {  // a zero byte
             return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u;
           };

@@ -1,7 +1,7 @@
 """Helper for tests/test_gpu_variants.py (run as a script on the GPU box): one process's somatic
 and germline records over a synthetic 60x / 30x pair, printed as one JSON line.  The kernel
-variants the library picks from the environment once per process (GQ_CALL_SPLIT, GQ_CALL_WPE,
-GQ_FILL_U) are compared across processes by the test."""
+paths the library picks from the environment once per process (GQ_GERM, GQ_SOM, GQ_ROWS) are
+compared across processes by the test."""
 import hashlib
 import json
 import math
