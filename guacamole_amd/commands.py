@@ -720,6 +720,87 @@ def vaf_histogram_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def allele_evidence_reads(ctx: native.Context, rs: ReadSet, loci, **params) -> List[dict]:
+    """AlleleEvidence (variants/AlleleEvidence.scala:58-101) of every distinct allele of every
+    sample's pileup at the loci pileupFlatMap(reads, partitions, skipEmpty=true) visits
+    (gq_allele_evidence).  params: min_mapq (1), variants_only (True).  Rows dict(contig (name),
+    locus, sample (slot), ref, alt, evidence (native.EVIDENCE_FIELDS order), flags), loci in call
+    order, samples ascending, a sample's alleles by (ref, alt)."""
+    res = ctx.allele_evidence(device_reads(ctx, rs), loci, **params)
+    rows = []
+    for r in res.rows:
+        r = dict(r)
+        r["contig"] = rs.contig_names[r["contig"]]
+        rows.append(r)
+    return rows
+
+
+ALLELE_EVIDENCE_HEADER = ("contig,locus,sample,ref,alt,readDepth,alleleReadDepth,forwardDepth,alleleForwardDepth,"
+                          "meanMappingQuality,medianMappingQuality,meanBaseQuality,medianBaseQuality,"
+                          "medianMismatchesPerRead,flags")
+
+
+def write_allele_evidence_csv(path: str, rows: List[dict], sample_names: Sequence[str]) -> None:
+    """The rows of allele_evidence_reads as CSV (ALLELE_EVIDENCE_HEADER): the sample by name, the
+    nine evidence fields after the likelihood, doubles as repr() writes them (they read back to the
+    same bits), NaN as "NaN".  Refuses an existing path."""
+    def num(x) -> str:
+        if isinstance(x, float):
+            return "NaN" if x != x else repr(x)
+        return str(x)
+    with open(path, "x") as fh:
+        fh.write(ALLELE_EVIDENCE_HEADER + "\n")
+        for r in rows:
+            s = r["sample"]
+            name = sample_names[s] if s < len(sample_names) else "default"
+            fh.write(",".join([r["contig"], str(r["locus"]), name, r["ref"], r["alt"]] +
+                              [num(x) for x in r["evidence"][1:]] + [str(r["flags"])]) + "\n")
+
+
+def allele_evidence_main(argv: Sequence[str]) -> int:
+    """allele-evidence: the evidence table of every allele at every variant locus (--all-loci: at
+    every visited locus) of one BAM, as CSV.  Input filters as germline-standard's
+    (GermlineStandardCaller.scala:53-54)."""
+    import os
+    p = argparse.ArgumentParser(prog="allele-evidence",
+                                description="per-allele evidence (depths, strand depths, mapping / base quality, "
+                                            "mismatches) at every variant locus")
+    p.add_argument("--reads", required=True)
+    p.add_argument("--out", required=True, help="Output CSV path (must not exist)")
+    p.add_argument("--loci", default="", help="Loci to visit (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    p.add_argument("--min-mapq", type=int, default=1, help="Minimum read mapping quality for a read (Phred-scaled)")
+    p.add_argument("--all-loci", action="store_true", help="Every visited locus, not only those with a non-Match element")
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("allele-evidence")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    builder = _loci_builder(args)
+    filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
+    ctx = None
+    rs = None
+    if device_ingest(args, args.reads):
+        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
+        ctx = native.Context(args.device)
+        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
+    if rs is None:
+        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    loci = builder.result(rs.contig_lengths_map)
+    parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
+    flat = flatten_partitions(parts, rs.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    rows = allele_evidence_reads(ctx, rs, flat, min_mapq=args.min_mapq, variants_only=not args.all_loci)
+    write_allele_evidence_csv(args.out, rows, rs.sample_names)
+    print("Wrote %d allele evidence rows." % len(rows), file=sys.stderr)
+    return 0
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -732,7 +813,7 @@ def warn_default_parallelism(args, world: int) -> None:
 
 
 def single_process_only(command: str) -> None:
-    """germline-standard, variant-support and vaf-histogram run as one process on --device: under
+    """germline-standard, variant-support, vaf-histogram and allele-evidence run as one process on --device: under
     torch.distributed.run every rank would repeat the whole job and write the same output, so a
     multi-rank launch is refused."""
     import os
@@ -757,7 +838,7 @@ def _finish_rank(rc: int) -> int:
 
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
-            "germline-standard": germline_standard_main}
+            "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

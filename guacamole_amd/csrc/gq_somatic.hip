@@ -1253,6 +1253,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   }
 }
 
+#include "gq_allele_evidence.h"
+
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
   const int key = 2 * min_mapq + (incl_align ? 1 : 0);  // the projection's filter and probability model
   if (t->mproj && t->mproj_mapq == key) return GQ_OK;
@@ -2256,6 +2258,228 @@ gq_status gq_germline_standard(gq_ctx *c, const gq_dev_reads *rd, const gq_loci 
   c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
   *out = res;
   return GQ_OK;
+}
+
+gq_status gq_allele_evidence(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                             const gq_allele_evidence_params *p, gq_allele_evidence_rows **out) {
+  if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_allele_evidence: null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  const auto h0 = std::chrono::steady_clock::now();
+  c->timings = gq_timings{};
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  Plan pl;
+  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
+  if (st) return st;
+  st = plan(c, rd, loci, kAeT, pl, c->tiles);
+  if (st) return st;
+  gq_allele_evidence_rows *res = (gq_allele_evidence_rows *)calloc(1, sizeof(gq_allele_evidence_rows));
+  if (!res) return set_err(GQ_E_NOMEM, "calloc");
+  auto fail = [&](gq_status e) {
+    gq_free_allele_evidence(res);
+    return e;
+  };
+  if (pl.n_tiles == 0) {
+    *out = res;
+    return GQ_OK;
+  }
+  // pileup element order: each window's first visited locus and initial (heap-ordered) group
+  SomWin sw{};
+  st = build_somwin(c, pl, rd, rd, sw);
+  if (st) return fail(st);
+  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+    c->n_cu = 256;
+  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
+                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
+                     rec_cap = 1 << 16, pool_cap = 1 << 16, amb_cap = 4096, deep_cap = 4096;
+  Counters hc{};
+  int64_t n_items = 0;
+  for (int attempt = 0;; ++attempt) {
+    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
+    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
+    HIP_TRY(c->srecs.ensure(rec_cap * sizeof(AeRec)));
+    HIP_TRY(c->pool.ensure(pool_cap));
+    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
+    Counters *ctr = (Counters *)c->counters.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    // the loci to process, found tile-wise (a few resident workgroups per CU over the tiles)
+    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
+                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)p->min_mapq,
+                       (int)p->variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hc.err) break;
+    if (hc.n_complex > item_cap) {
+      if (attempt == 2) return fail(set_err(GQ_E_CAPACITY, "allele-evidence: locus list capacity retries exhausted"));
+      item_cap = hc.n_complex + 1024;
+      continue;
+    }
+    n_items = (int64_t)hc.n_complex;
+    if (n_items == 0) break;
+    int64_t *dl = (int64_t *)c->deep_list.p;
+    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
+    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
+    // mode, its per-wave scratch sized from the deepest of them
+    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
+                        int64_t n_ain) -> gq_status {
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
+      if (nd <= 0 || hc.err) return GQ_OK;
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
+      const int64_t waves = std::min<int64_t>(nd, 256);
+      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
+      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
+      hipLaunchKernelGGL(allele_evidence_call<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)), dim3(kBlock),
+                         0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p,
+                         (AeRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, aout, acap, ain, aref,
+                         n_ain, deep);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      return GQ_OK;
+    };
+    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
+    hipLaunchKernelGGL(allele_evidence_call<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
+                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, (AeRec *)c->srecs.p,
+                       rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, (AmbItem *)c->amb.p, amb_cap,
+                       (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, fast);
+    HIP_TRY(hipGetLastError());
+    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
+    if (st) return fail(st);
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    bool retry = false;
+    if (hc.n_amb > amb_cap) {
+      amb_cap = hc.n_amb + 1024;
+      retry = true;
+    }
+    if (hc.n_deep > deep_cap) {
+      deep_cap = hc.n_deep + 1024;
+      retry = true;
+    }
+    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
+      std::vector<AmbItem> amb((size_t)hc.n_amb);
+      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(c->amb_ref.ensure(amb.size()));
+      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
+      if (st) return fail(st);
+      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
+      const int64_t from = (int64_t)hc.n_deep;
+      hipLaunchKernelGGL(allele_evidence_call<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p,
+                         (AeRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, (AmbItem *)nullptr,
+                         (unsigned long long)0, (const AmbItem *)c->amb.p, (const uint8_t *)c->amb_ref.p,
+                         (int64_t)amb.size(), fast);
+      HIP_TRY(hipGetLastError());
+      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
+      if (st) return fail(st);
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+      if (hc.n_deep > deep_cap) {
+        deep_cap = hc.n_deep + 1024;
+        retry = true;
+      }
+    }
+    if (hc.n_rec > rec_cap) {
+      rec_cap = hc.n_rec + 1024;
+      retry = true;
+    }
+    if (hc.pool_used > pool_cap) {
+      pool_cap = hc.pool_used + 4096;
+      retry = true;
+    }
+    if (!retry || hc.err) break;
+    if (attempt == 2) return fail(set_err(GQ_E_CAPACITY, "allele-evidence: output capacity retries exhausted"));
+  }
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  st = check_device_error(c, hc);
+  if (st) return fail(st);
+  const int64_t nr = n_items > 0 ? (int64_t)hc.n_rec : 0;
+  std::vector<AeRec> recs((size_t)nr);
+  std::vector<uint8_t> hpool((size_t)std::min<unsigned long long>(hc.pool_used, pool_cap));
+  if (nr) HIP_TRY(hipMemcpyAsync(recs.data(), c->srecs.p, (size_t)nr * sizeof(AeRec), hipMemcpyDeviceToHost, c->stream));
+  if (!hpool.empty()) HIP_TRY(hipMemcpyAsync(hpool.data(), c->pool.p, hpool.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const auto m0 = std::chrono::steady_clock::now();
+  // rows by key: loci in call order, samples ascending, a sample's alleles by (ref, alt) bytes
+  std::vector<uint32_t> ord((size_t)nr);
+  for (int64_t k = 0; k < nr; ++k) ord[(size_t)k] = (uint32_t)k;
+  std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return recs[x].key < recs[y].key; });
+  const size_t N = (size_t)std::max<int64_t>(nr, 1);
+  size_t pool_len = 0;
+  for (const AeRec &r : recs) pool_len += (size_t)r.ref_len + r.alt_len;
+  res->contig = (int32_t *)malloc(N * 4);
+  res->pos = (int64_t *)malloc(N * 8);
+  res->sample = (int32_t *)malloc(N * 4);
+  res->ref_off = (int64_t *)malloc(N * 8);
+  res->alt_off = (int64_t *)malloc(N * 8);
+  res->ref_len = (int32_t *)malloc(N * 4);
+  res->alt_len = (int32_t *)malloc(N * 4);
+  res->evidence = (gq_evidence *)malloc(N * sizeof(gq_evidence));
+  res->flags = (uint8_t *)malloc(N);
+  res->allele_pool = (uint8_t *)malloc(std::max<size_t>(pool_len, 1));
+  if (!res->contig || !res->pos || !res->sample || !res->ref_off || !res->alt_off || !res->ref_len || !res->alt_len ||
+      !res->evidence || !res->flags || !res->allele_pool)
+    return fail(set_err(GQ_E_NOMEM, "allele-evidence result of %lld rows", (long long)nr));
+  size_t at = 0;
+  for (int64_t q = 0; q < nr; ++q) {
+    const AeRec &r = recs[ord[(size_t)q]];
+    const int tot = r.ref_len + r.alt_len;
+    res->contig[q] = r.contig;
+    res->pos[q] = r.pos;
+    res->sample[q] = r.sample;
+    res->ref_len[q] = r.ref_len;
+    res->alt_len[q] = r.alt_len;
+    res->ref_off[q] = (int64_t)at;
+    res->alt_off[q] = (int64_t)at + r.ref_len;
+    res->evidence[q] = r.ev;
+    res->flags[q] = r.flags;
+    for (int i = 0; i < tot; ++i)
+      res->allele_pool[at + (size_t)i] = tot <= 8 ? (uint8_t)(r.allele >> (8 * i)) : hpool[(size_t)r.allele + (size_t)i];
+    at += (size_t)tot;
+  }
+  res->n = nr;
+  res->pool_len = (int64_t)pool_len;
+  res->visited_loci = (int64_t)hc.visited;
+  res->listed_loci = n_items;
+  c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timings.pileup_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+  c->timings.complex_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+  c->timings.finalize_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
+  c->timings.total_ms = ms;
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = pl.n_tiles;
+  c->timings.deep_loci = (int64_t)hc.n_deep;
+  c->timings.deep_max = (int64_t)hc.deep_max;
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  *out = res;
+  return GQ_OK;
+}
+
+void gq_free_allele_evidence(gq_allele_evidence_rows *r) {
+  if (!r) return;
+  free(r->contig);
+  free(r->pos);
+  free(r->sample);
+  free(r->ref_off);
+  free(r->alt_off);
+  free(r->ref_len);
+  free(r->alt_len);
+  free(r->allele_pool);
+  free(r->evidence);
+  free(r->flags);
+  free(r);
 }
 
 void gq_free_somatic(gq_somatic_calls *r) {

@@ -75,6 +75,10 @@ GERMLINE_STD_DEFAULTS = dict(min_mapq=1, min_read_depth=0, max_read_depth=2 ** 3
                              min_likelihood=0, apply_filters=1)
 
 
+class gq_allele_evidence_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("variants_only", C.c_int32)]
+
+
 class gq_vaf_params(C.Structure):
     _fields_ = [("bins", C.c_int32), ("min_read_depth", C.c_int32), ("min_vaf", C.c_int32)]
 
@@ -148,6 +152,14 @@ class gq_somatic_calls(C.Structure):
                 ("block_", C.c_void_p)]
 
 
+class gq_allele_evidence_rows(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int64)),
+                ("sample", C.POINTER(C.c_int32)), ("ref_off", C.POINTER(C.c_int64)), ("ref_len", C.POINTER(C.c_int32)),
+                ("alt_off", C.POINTER(C.c_int64)), ("alt_len", C.POINTER(C.c_int32)),
+                ("allele_pool", C.POINTER(C.c_uint8)), ("pool_len", C.c_int64), ("evidence", C.POINTER(gq_evidence)),
+                ("flags", C.POINTER(C.c_uint8)), ("visited_loci", C.c_int64), ("listed_loci", C.c_int64)]
+
+
 EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timings", "gq_set_tile", "gq_reads_upload",
             "gq_reads_wrap_device", "gq_reads_free", "gq_reads_rederive", "gq_germline_threshold", "gq_germline_threshold_device",
             "gq_free_calls", "gq_pileup_counts",
@@ -157,7 +169,7 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_bam_dev_n_contigs", "gq_bam_dev_contig_name", "gq_bam_dev_contig_length", "gq_bam_dev_scan",
             "gq_bam_dev_reads", "gq_reads_positions", "gq_reads_contig_begin", "gq_reads_download", "gq_bam_dev_map",
             "gq_bam_dev_load", "gq_bam_dev_map_ex", "gq_bam_dev_plan", "gq_bam_dev_plan_segments",
-            "gq_write_vcf_germline")
+            "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence")
 
 
 def lib():
@@ -175,7 +187,7 @@ def lib():
                   "gq_reads_rederive",
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
-                  "gq_germline_standard"):
+                  "gq_germline_standard", "gq_allele_evidence"):
             getattr(L, f).restype = C.c_int
         L.gq_germline_threshold.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_params),
                                             C.POINTER(C.POINTER(gq_calls))]
@@ -194,6 +206,10 @@ def lib():
         L.gq_free_allele_counts.argtypes = [C.POINTER(gq_allele_counts)]
         L.gq_germline_standard.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_std_params),
                                            C.POINTER(C.POINTER(gq_somatic_calls))]
+        L.gq_allele_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_allele_evidence_params),
+                                         C.POINTER(C.POINTER(gq_allele_evidence_rows))]
+        L.gq_free_allele_evidence.argtypes = [C.POINTER(gq_allele_evidence_rows)]
+        L.gq_free_allele_evidence.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -419,6 +435,19 @@ class Context:
         out = C.POINTER(gq_somatic_calls)()
         _check(lib().gq_germline_standard(self.h, reads.h, C.byref(L), C.byref(ps), C.byref(out)))
         return SomaticCalls.from_result(out)
+
+    def allele_evidence(self, reads: "DeviceReads", loci, min_mapq: int = 1,
+                        variants_only: bool = True) -> "AlleleEvidenceRows":
+        """gq_allele_evidence: AlleleEvidence for every distinct allele of every sample at the visited
+        loci (variants_only: at the loci whose filtered pileup holds a non-Match element)."""
+        L, keep = make_gq_loci(*loci)
+        prm = gq_allele_evidence_params(int(min_mapq), int(bool(variants_only)))
+        out = C.POINTER(gq_allele_evidence_rows)()
+        _check(lib().gq_allele_evidence(self.h, reads.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return AlleleEvidenceRows.from_struct(out.contents)
+        finally:
+            lib().gq_free_allele_evidence(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:
@@ -686,3 +715,48 @@ class SomaticCalls:
             off += nb
         return SomaticCalls(cols, buf[off:off + pl].tobytes(), visited, cands)
 
+
+
+class AlleleEvidenceRows:
+    """gq_allele_evidence's rows in output order: numpy columns copied out of the library's
+    result, row dicts built on first use of ``rows``."""
+
+    COLUMNS = ("contig", "pos", "sample", "ref_off", "ref_len", "alt_off", "alt_len", "evidence", "flags")
+
+    def __init__(self, cols: Dict[str, np.ndarray], pool: bytes, visited: int, listed: int):
+        self.cols, self.pool, self.visited_loci, self.listed_loci = cols, pool, visited, listed
+        self._rows: Optional[List[dict]] = None
+
+    @staticmethod
+    def from_struct(c: gq_allele_evidence_rows) -> "AlleleEvidenceRows":
+        n = int(c.n)
+        pool = C.string_at(c.allele_pool, c.pool_len) if c.pool_len else b""
+        cols = {}
+        for k in AlleleEvidenceRows.COLUMNS:
+            t = getattr(c, k)._type_
+            dt = np.dtype(_EVIDENCE_DTYPE) if t is gq_evidence else np.dtype(t)
+            if n:
+                buf = (C.c_uint8 * (n * dt.itemsize)).from_address(C.cast(getattr(c, k), C.c_void_p).value)
+                cols[k] = np.frombuffer(buf, dtype=dt, count=n).copy()
+            else:
+                cols[k] = np.zeros(0, dt)
+        return AlleleEvidenceRows(cols, pool, int(c.visited_loci), int(c.listed_loci))
+
+    def __len__(self) -> int:
+        return int(self.cols["pos"].shape[0])
+
+    @property
+    def rows(self) -> List[dict]:
+        """dict(contig (index), locus, sample (slot), ref, alt, evidence (EVIDENCE_FIELDS order), flags)."""
+        if self._rows is None:
+            c, pool = self.cols, self.pool
+            # columns to Python lists once, as SomaticCalls.rows
+            L = {k: c[k].tolist() for k in ("contig", "pos", "sample", "ref_off", "ref_len", "alt_off", "alt_len",
+                                            "flags")}
+            ev = list(zip(*[c["evidence"][k].tolist() for k in EVIDENCE_FIELDS])) if len(self) else []
+            self._rows = [dict(contig=ct, locus=ps, sample=sm, ref=pool[ro:ro + rl].decode("latin-1"),
+                               alt=pool[ao:ao + al].decode("latin-1"), evidence=e, flags=fl)
+                          for ct, ps, sm, ro, rl, ao, al, fl, e in
+                          zip(L["contig"], L["pos"], L["sample"], L["ref_off"], L["ref_len"], L["alt_off"],
+                              L["alt_len"], L["flags"], ev)]
+        return self._rows

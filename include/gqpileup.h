@@ -450,6 +450,40 @@ typedef struct {
 gq_status gq_germline_standard(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
                                const gq_germline_std_params *params, gq_somatic_calls **out);
 
+/* allele-evidence: AlleleEvidence.apply (variants/AlleleEvidence.scala:58-101) for EVERY distinct
+ * allele of every sample's pileup, at the loci pileupFlatMap(reads, partitions, skipEmpty = true)
+ * visits: what a callback handed to pileupFlatMap could compute itself from the whole pileup.
+ * Elements of reads with mapq < min_mapq are dropped first (QualityAlignedReadsFilter,
+ * PileupElementsFilter.scala:25-36); the pileup's reference base is the unfiltered pileup's, as in
+ * the callers.  With variants_only, only loci whose filtered pileup holds a non-Match element
+ * (VariantLocus.apply's depth > referenceDepth, commands/VAFHistogram.scala:31-37) are processed.
+ * One row per (locus, sample present in the filtered pileup (Pileup.bySample, Pileup.scala:57-61),
+ * distinct allele of that sample's filtered pileup); read_depth / forward_depth are that sample's
+ * filtered pileup's, the means run in pileup element order.  Rows: loci in call order, samples
+ * ascending, alleles by (ref, alt) bytes.  Loci whose filtered pileup is empty give no row.     */
+typedef struct {
+  int32_t min_mapq;        /* keep elements with read mapq >= min_mapq; 0 keeps all */
+  int32_t variants_only;   /* 1: only loci with a non-Match element after the filter */
+} gq_allele_evidence_params;
+typedef struct {
+  int64_t n;
+  int32_t *contig;  int64_t *pos;  int32_t *sample;
+  int64_t *ref_off; int32_t *ref_len; int64_t *alt_off; int32_t *alt_len;   /* into allele_pool */
+  uint8_t *allele_pool; int64_t pool_len;
+  gq_evidence *evidence;   /* likelihood = 0.0; the other nine fields as AlleleEvidence.apply */
+  uint8_t *flags;          /* bit0: reference base taken from heap order (MD tags disagree) */
+  int64_t visited_loci;    /* loci whose filtered pileup is not empty               */
+  int64_t listed_loci;     /* loci handed to the per-locus kernel (variants_only: the variant loci) */
+} gq_allele_evidence_rows;
+#ifdef __cplusplus
+static_assert(sizeof(gq_evidence) == 64, "gq_evidence layout");
+static_assert(sizeof(gq_allele_evidence_params) == 8, "gq_allele_evidence_params layout");
+static_assert(sizeof(gq_allele_evidence_rows) == 112, "gq_allele_evidence_rows layout");
+#endif
+gq_status gq_allele_evidence(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
+                             const gq_allele_evidence_params *params, gq_allele_evidence_rows **out);
+void gq_free_allele_evidence(gq_allele_evidence_rows *rows);
+
 /* vaf-histogram: VAFHistogram.variantLociFromReads + generateVAFHistogram
  * (commands/VAFHistogram.scala:208-229, 188-196): at every visited locus whose pileup holds a
  * non-Match element (VariantLocus.apply, :31-37), VAF = (depth - referenceDepth).toFloat /
