@@ -162,24 +162,72 @@ __device__ __forceinline__ void germline_decide(const uint32_t *cnt, const Tile 
   }
 }
 
+// Exclusive offsets of the per-partition counts (clamped to the capacity) of one output kind,
+// their total (n_rec / n_complex) and the largest overflow (part_max); one block of NT threads,
+// kParts / NT partitions each.
+template <int NT>
+__device__ __forceinline__ void part_scan_block(Counters *ctr, int which, const OutGeom &og) {
+  static_assert(kParts % NT == 0, "partitions per thread");
+  constexpr int PER = kParts / NT;
+  __shared__ unsigned long long s[NT];
+  __shared__ unsigned long long mx;
+  const int t = threadIdx.x;
+  unsigned long long v[PER], sum = 0, m = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const unsigned long long x = ctr->part[which][t * PER + j];
+    const unsigned long long cap = og.cap(which, t * PER + j);
+    m = x > cap && x - cap > m ? x - cap : m;  // largest overflow
+    v[j] = x < cap ? x : cap;
+    sum += v[j];
+  }
+  if (t == 0) mx = 0;
+  s[t] = sum;
+  __syncthreads();
+  if (m) atomicMax(&mx, m);
+  for (int d = 1; d < NT; d <<= 1) {
+    const unsigned long long y = t >= d ? s[t - d] : 0ull;
+    __syncthreads();
+    s[t] += y;
+    __syncthreads();
+  }
+  unsigned long long o = s[t] - sum;  // exclusive
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    ctr->part_off[which][t * PER + j] = o;
+    o += v[j];
+  }
+  if (t == NT - 1) {
+    ctr->part_off[which][kParts] = s[t];
+    if (which == 0) ctr->n_rec = s[t];
+    else ctr->n_complex = s[t];
+    ctr->part_max[which] = mx;  // 0: every partition within its capacity
+  }
+}
+
 // The variant candidates of germline_decide -> Genotype records, one thread per record slot
 // (GermlineThresholdCaller.scala:100-177 for a pileup of single-base alleles; counts < 2^16).
 // Allele (ref, b) keys: count << 16 | (255 - Scala map rank) << 8 | category: sorting the keys
 // descending = sortBy(-count), a stable sort of the counts map's iteration order
 // (GermlineThresholdCaller.scala:103-104, gq_scala_order.h).  Unused slots get a key past
 // every ordinal (dead_key) and are counted in n_dead; they sort behind the live records.
-__global__ void germline_expand(CallRec *__restrict__ recs, Counters *ctr, OutGeom og, int threshold,
-                                int emit_ref, int emit_no_call, uint64_t dead_key) {
-  const unsigned long long n = ctr->n_rec;
+//
+// The records' partition offsets (part_scan_block, which = 0) are due between the kernels that
+// append records and the finalize chain; this kernel appends none (it rewrites reserved slots),
+// so its first workgroup computes them on the side and the chain behind it finds them in place:
+// no launch of their own.  A partition's kept count is read from its counter directly.
+__global__ __launch_bounds__(kBlock) void germline_expand(CallRec *__restrict__ recs, Counters *ctr, OutGeom og,
+                                                          int threshold, int emit_ref, int emit_no_call,
+                                                          uint64_t dead_key) {
+  if (blockIdx.x == 0) part_scan_block<kBlock>(ctr, 0, og);
   const int64_t thr1 = (int64_t)threshold + 1;
   auto passes = [=](uint32_t count, uint32_t depth) { return (int64_t)count * 100 >= thr1 * (int64_t)depth; };
   constexpr uint64_t kAltSym = ((uint64_t)'<' << 8) | ((uint64_t)'A' << 16) | ((uint64_t)'L' << 24) |
                                ((uint64_t)'T' << 32) | ((uint64_t)'>' << 40);
   unsigned dead = 0, ties = 0;
-  (void)n;
   // partition by partition (block per partition): its slots [0, kept count)
   for (int p = blockIdx.x; p < kParts; p += gridDim.x) {
-   const unsigned long long cnt = ctr->part_off[0][p + 1] - ctr->part_off[0][p];
+   const unsigned long long cnt = min(ctr->part[0][p], og.cap(0, p));
    for (unsigned long long k = threadIdx.x; k < cnt; k += blockDim.x) {
     const unsigned long long slot = og.slot(0, p, k);
     const CallRec cand = recs[slot];

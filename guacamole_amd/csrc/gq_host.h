@@ -1007,7 +1007,6 @@ struct gq_ctx {
   gq::DevBuf deep_list, deep_scratch;              // somatic: the deep caller's list and per-wave scratch
   gq::DevBuf cands;                                // somatic: the candidates' records (CandRec)
   gq::DevBuf win_bound;                            // germline: window bounds (window_bounds)
-  gq::DevBuf bkt;                                  // germline output order: bucket counts / offsets / fill
   // The bulk host -> device staging (H2DStager): two pinned chunks kept for the context's life
   // and allocated by `prep`, a helper thread gq_open starts (pinning 128 MB takes ~20 ms, and
   // freeing it as long: neither belongs on a load's path).  prep also loads the library's code
@@ -1110,6 +1109,16 @@ struct gq_dev_reads {
   hipEvent_t tev[6] = {};
   unsigned pending = 0;            // 1: derivation span, 2: projection span, fill and proj_reads
   unsigned long long *nok = nullptr;  // proj_prep's spread counters (kOkSpread words) while pending & 2
+  // What the first derivation learned from input arrays a re-derivation does not rewrite
+  // (pmax_end, contig_read_begin, the pool's order): a re-derivation reuses it and makes no host
+  // round trip.  Its validation flag (read_prep) goes to pinned memory behind the kernel and is
+  // checked once the stream has passed it (gq::validation_settled).
+  bool shape_kept = false;
+  int64_t *qoff_dev = nullptr;     // the slices' offsets per contig (n_contigs + 1; in `owned`)
+  int64_t n_slices_kept = 0;
+  int pool_ordered_kept = 0;
+  int *vflag = nullptr;            // pinned: the last re-derivation's validation flag
+  bool vflag_pending = false;      // a re-derivation's flag has not been checked yet
   mutable void *mproj = nullptr;  // somatic margin projection (a biased byte per locus-read), for mproj_mapq
   mutable int mproj_mapq = -1;
   mutable void *mnb = nullptr;    // per slice: 1 if a margin term there is kMargin8None (no bound)
@@ -1195,6 +1204,11 @@ struct H2DStager {
 // Upload-time derivation of a resident read set whose SoA arrays (and host copy of
 // contig_read_begin) are in place: validation, read shape, projection pool, block index.
 gq_status derive_shape(gq_ctx *c, gq_dev_reads *d, int64_t md_len);
+// The validation flag of a re-derivation that did not wait for it: validation_settled checks it
+// after the caller has waited for the stream, validation_wait waits for the derivation itself
+// (an entry point calls one of them before it returns anything computed from the set).
+gq_status validation_settled(const gq_dev_reads *d);
+gq_status validation_wait(const gq_dev_reads *d);
 // The column records (ColDesc, the auxiliary list, clean / N-base counts), derived on first use.
 gq_status ensure_columns(gq_ctx *c, const gq_dev_reads *d);
 // ev_rb (the read base under each MD event) of a resident read set, derived on first use

@@ -1684,45 +1684,9 @@ __host__ __device__ inline CallsLayout calls_layout(int64_t n, int64_t dev_pool_
   return L;
 }
 
-// Exclusive offsets of the per-partition counts (clamped to the capacity) of one output kind,
-// their total (n_rec / n_complex) and the largest count (part_max); one block of 1024
-// threads, kParts / 1024 partitions each.
+// part_scan_block (gq_germline_common.h) as a launch of its own: one block of 1024 threads.
 __global__ __launch_bounds__(1024) void part_scan(Counters *ctr, int which, OutGeom og) {
-  constexpr int PER = kParts / 1024;
-  __shared__ unsigned long long s[1024];
-  __shared__ unsigned long long mx;
-  const int t = threadIdx.x;
-  unsigned long long v[PER], sum = 0, m = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const unsigned long long x = ctr->part[which][t * PER + j];
-    const unsigned long long cap = og.cap(which, t * PER + j);
-    m = x > cap && x - cap > m ? x - cap : m;  // largest overflow
-    v[j] = x < cap ? x : cap;
-    sum += v[j];
-  }
-  if (t == 0) mx = 0;
-  s[t] = sum;
-  __syncthreads();
-  if (m) atomicMax(&mx, m);
-  for (int d = 1; d < 1024; d <<= 1) {
-    const unsigned long long y = t >= d ? s[t - d] : 0ull;
-    __syncthreads();
-    s[t] += y;
-    __syncthreads();
-  }
-  unsigned long long o = s[t] - sum;  // exclusive
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    ctr->part_off[which][t * PER + j] = o;
-    o += v[j];
-  }
-  if (t == 1023) {
-    ctr->part_off[which][kParts] = s[t];
-    if (which == 0) ctr->n_rec = s[t];
-    else ctr->n_complex = s[t];
-    ctr->part_max[which] = mx;  // 0: every partition within its capacity
-  }
+  part_scan_block<1024>(ctr, which, og);
 }
 
 // Dense (key, slot) pairs of the partitioned records, for the radix sort.
@@ -1787,6 +1751,18 @@ __global__ void bucket_scatter(const Counters *__restrict__ ctr, const int64_t *
   }
 }
 
+// calls_image works in kImgBlocks contiguous chunks of the n records (output order); the pool
+// offsets are a scan of the records' allele lengths: chunk sums (img_sums), then inside
+// calls_image each workgroup's sum of the chunks before its own and its chunk's own scan.
+// (Adding a record's length to its chunk's sum from bucket_rank instead was measured: the
+// atomics on 512 words took bucket_rank from 8 to 70 us on the 30x chr20 shard.)
+__device__ __forceinline__ void img_chunk(int64_t n, int64_t &a, int64_t &b) {
+  const int64_t per = (n + kImgBlocks - 1) / kImgBlocks;
+  a = min(n, (int64_t)blockIdx.x * per);
+  b = min(n, a + per);
+}
+__device__ __forceinline__ uint32_t rec_len(const CallRec &r) { return (uint32_t)r.ref_len + (uint32_t)r.alt_len; }
+
 __global__ void bucket_rank(int64_t nbk, const uint32_t *__restrict__ off, const int32_t *__restrict__ members,
                             const uint64_t *__restrict__ keys, const int32_t *__restrict__ slot,
                             const int64_t *__restrict__ bkt, int32_t *__restrict__ order) {
@@ -1811,19 +1787,9 @@ __global__ void iota_i32(int32_t *__restrict__ v, int64_t n) {
   if (i < n) v[i] = (int32_t)i;
 }
 
-// calls_image works in kImgBlocks contiguous chunks of the n records (output order); the pool
-// offsets are a scan of the records' allele lengths: chunk sums (img_sums), their exclusive
-// scan (img_scan, one workgroup), then each chunk's own scan inside calls_image.
-__device__ __forceinline__ void img_chunk(int64_t n, int64_t &a, int64_t &b) {
-  const int64_t per = (n + kImgBlocks - 1) / kImgBlocks;
-  a = min(n, (int64_t)blockIdx.x * per);
-  b = min(n, a + per);
-}
-__device__ __forceinline__ uint32_t rec_len(const CallRec &r) { return (uint32_t)r.ref_len + (uint32_t)r.alt_len; }
-
 __global__ __launch_bounds__(kBlock) void img_sums(const CallRec *__restrict__ recs, const int32_t *__restrict__ order,
                                                     const uint32_t *__restrict__ off, int64_t nbk,
-                                                    int64_t *__restrict__ bsum) {
+                                                    unsigned long long *__restrict__ bsum) {
   __shared__ unsigned long long red;
   if (threadIdx.x == 0) red = 0;
   __syncthreads();
@@ -1834,36 +1800,38 @@ __global__ __launch_bounds__(kBlock) void img_sums(const CallRec *__restrict__ r
   for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
   if ((threadIdx.x & 63) == 0 && s) atomicAdd(&red, s);
   __syncthreads();
-  if (threadIdx.x == 0) bsum[blockIdx.x] = (int64_t)red;
-}
-
-__global__ __launch_bounds__(kImgBlocks) void img_scan(int64_t *__restrict__ bsum) {  // in place, exclusive; total at [kImgBlocks]
-  __shared__ int64_t s[kImgBlocks];
-  const int t = threadIdx.x;
-  const int64_t v = bsum[t];
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kImgBlocks; d <<= 1) {
-    const int64_t y = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += y;
-    __syncthreads();
-  }
-  bsum[t] = s[t] - v;
-  if (t == kImgBlocks - 1) bsum[kImgBlocks] = s[t];
+  if (threadIdx.x == 0) bsum[blockIdx.x] = red;
 }
 
 __global__ __launch_bounds__(kBlock) void calls_image(const CallRec *__restrict__ recs, const int32_t *__restrict__ order,
                                                        const uint32_t *__restrict__ off, int64_t nbk,
-                                                       const int64_t *__restrict__ bsum, const uint8_t *__restrict__ dpool,
+                                                       const unsigned long long *__restrict__ bsum, const uint8_t *__restrict__ dpool,
                                                        Counters *__restrict__ ctr, uint8_t *__restrict__ img) {
   __shared__ uint32_t wsum[kBlock / 64];
+  __shared__ unsigned long long before_all[2];  // allele bytes of the chunks before this one | of every chunk
   const int64_t n = (int64_t)off[nbk];
   const CallsLayout L = calls_layout(n, 0);
   int64_t a, b;
   img_chunk(n, a, b);
-  int64_t prefix = bsum[blockIdx.x];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (threadIdx.x < 2) before_all[threadIdx.x] = 0;
+  __syncthreads();
+  {  // the chunk sums: kImgBlocks words, a few per thread
+    unsigned long long sb = 0, sa = 0;
+    for (int q = threadIdx.x; q < kImgBlocks; q += blockDim.x) {
+      const unsigned long long v = bsum[q];
+      sa += v;
+      sb += q < (int)blockIdx.x ? v : 0ull;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+      sa += __shfl_xor(sa, d, 64);
+      sb += __shfl_xor(sb, d, 64);
+    }
+    if (lane == 0 && sb) atomicAdd(&before_all[0], sb);
+    if (lane == 0 && sa) atomicAdd(&before_all[1], sa);
+  }
+  __syncthreads();
+  int64_t prefix = (int64_t)before_all[0];
   for (int64_t base = a; base < b; base += blockDim.x) {  // uniform trip count per workgroup
     const int64_t k = base + threadIdx.x;
     CallRec r{};
@@ -1901,7 +1869,7 @@ __global__ __launch_bounds__(kBlock) void calls_image(const CallRec *__restrict_
     prefix += all;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // header and the counters the host reads back
-    const int64_t pool_len = bsum[kImgBlocks];
+    const int64_t pool_len = (int64_t)before_all[1];
     reinterpret_cast<int64_t *>(img)[0] = pool_len;
     reinterpret_cast<int64_t *>(img)[1] = n;
     ctr->n_out = (unsigned long long)n;
@@ -1920,6 +1888,39 @@ __global__ void warm_k() {}
 hipError_t gq::warm_pileup(hipStream_t s) {
   hipLaunchKernelGGL(warm_k, dim3(1), dim3(64), 0, s);
   return hipGetLastError();
+}
+
+// read_prep's validation flag -> the status and message of a refused read set (0: valid).
+static gq_status validation_status(int bad) {
+  if (bad & 1)
+    return set_err(GQ_E_UNSORTED, "Regions must be sorted by start locus: reads are not sorted by (contig, start), "
+                                  "or pmax_end is not the running maximum of end within each contig");
+  if (bad & 2)
+    return set_err(GQ_E_ARG, "read set: an offset or length lies outside its pool, or a sample slot >= n_samples");
+  return GQ_OK;
+}
+
+// The validation flag of the set's last re-derivation, once the stream has passed its copy (the
+// caller has waited for the stream, or for an event recorded behind the copy): a set that no
+// longer validates is refused here as gq_reads_upload would have refused it.
+gq_status gq::validation_settled(const gq_dev_reads *dc) {
+  gq_dev_reads *d = const_cast<gq_dev_reads *>(dc);
+  if (!d->vflag_pending) return GQ_OK;
+  const int bad = *(volatile int *)d->vflag;
+  const gq_status vs = validation_status(bad);
+  if (vs) return vs;  // (stays pending: every later call on the set fails the same way)
+  if (((bad & 4) ? 0 : 1) != d->pool_ordered_kept)
+    return set_err(GQ_E_ARG, "read set: the sequence pool's order changed since the first derivation");
+  d->vflag_pending = false;
+  return GQ_OK;
+}
+
+// The same for an entry point that has not waited yet: wait for the derivation's end event.
+gq_status gq::validation_wait(const gq_dev_reads *d) {
+  if (!d || !d->vflag_pending) return GQ_OK;
+  HIP_TRY(hipSetDevice(d->ctx->device));
+  HIP_TRY(hipEventSynchronize(d->tev[1]));
+  return validation_settled(d);
 }
 
 extern "C" {
@@ -1976,7 +1977,7 @@ void gq_close(gq_ctx *c) {
   for (DevBuf *b : {&c->ranges, &c->tiles, &c->recs, &c->recs_sorted, &c->keys, &c->keys_sorted, &c->idx,
                     &c->idx_sorted, &c->cplx, &c->pool, &c->counters, &c->sort_tmp, &c->image, &c->tiles2, &c->srecs, &c->c_depth, &c->c_pos,
                     &c->c_base, &c->c_indel, &c->c_ref, &c->c_rb, &c->c_amb, &c->slow, &c->amb, &c->amb_ref,
-                    &c->heap_off, &c->heap_reads, &c->win_meta, &c->win_grp, &c->bkt})
+                    &c->heap_off, &c->heap_reads, &c->win_meta, &c->win_grp})
     b->release();
   for (auto &e : c->ev) (void)hipEventDestroy(e);
   for (auto &e : c->dev_ev) (void)hipEventDestroy(e);
@@ -2016,6 +2017,8 @@ static gq_status settle_stats(gq_dev_reads *d) {
   if (d->pending & 1) {
     HIP_TRY(hipEventSynchronize(d->tev[1]));
     (void)hipEventElapsedTime(&d->derive_dev_ms, d->tev[0], d->tev[1]);
+    const gq_status vs = gq::validation_settled(d);  // (its flag arrived before tev[1])
+    if (vs) return vs;
   }
   if (d->pending & 2) {
     HIP_TRY(hipEventSynchronize(d->tev[5]));
@@ -2049,6 +2052,7 @@ static gq_status derive_shape_impl(gq_ctx *c, gq_dev_reads *d, int64_t md_len, b
   d->ev_bases = false;
   int unordered = 0;
   const int nc = d->d.n_contigs;
+  const bool reuse = lazy && d->shape_kept;  // (a re-derivation: nothing below waits for the device)
   std::vector<int32_t> last((size_t)nc, 0);  // each contig's largest read end (pmax_end of its last read)
   if (d->d.n_reads > 0) {
     void *flag = nullptr;
@@ -2058,35 +2062,54 @@ static gq_status derive_shape_impl(gq_ctx *c, gq_dev_reads *d, int64_t md_len, b
     // validation and the read shapes in one pass (a read out of its pools gets no shape)
     hipLaunchKernelGGL(read_prep, dim3(nb), dim3(kBlock), 0, c->stream, d->d, (int *)flag, (int16_t *)p);
     HIP_TRY(hipGetLastError());
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    const auto &crb = d->contig_read_begin;
-    for (int k = 0; k < nc; ++k)
-      if (crb[(size_t)k + 1] > crb[(size_t)k])
-        HIP_TRY(hipMemcpyAsync(&last[(size_t)k], d->d.pmax_end + (crb[(size_t)k + 1] - 1), sizeof(int32_t),
-                               hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (bad & 1)
-      return set_err(GQ_E_UNSORTED, "Regions must be sorted by start locus: reads are not sorted by (contig, start), "
-                                    "or pmax_end is not the running maximum of end within each contig");
-    if (bad & 2)
-      return set_err(GQ_E_ARG, "read set: an offset or length lies outside its pool, or a sample slot >= n_samples");
-    unordered = (bad & 4) ? 1 : 0;
+    if (reuse) {
+      // the flag travels behind the kernel; whoever next waits for the stream checks it
+      // (validation_settled: settle_stats, or the next call on the set)
+      if (!d->vflag) HIP_TRY(hipHostMalloc((void **)&d->vflag, sizeof(int), hipHostMallocDefault));
+      *d->vflag = 0;
+      HIP_TRY(hipMemcpyAsync(d->vflag, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      d->vflag_pending = true;
+      unordered = d->pool_ordered_kept ? 0 : 1;
+    } else {
+      int bad = 0;
+      HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      const auto &crb = d->contig_read_begin;
+      for (int k = 0; k < nc; ++k)
+        if (crb[(size_t)k + 1] > crb[(size_t)k])
+          HIP_TRY(hipMemcpyAsync(&last[(size_t)k], d->d.pmax_end + (crb[(size_t)k + 1] - 1), sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const gq_status vs = validation_status(bad);
+      if (vs) return vs;
+      unordered = (bad & 4) ? 1 : 0;
+    }
   }
   {  // the projections' slices (whole 512-locus blocks up to each contig's largest read end) and
      // the block index of the reads (plan_tiles' windows of aligned tiles); the projection
      // itself is derived on first use (ensure_projection)
-    std::vector<int64_t> qoff((size_t)nc + 1, 0);
-    for (int k = 0; k < nc; ++k) {
-      const int64_t col1 = ((int64_t)std::max(last[(size_t)k], 0) + 7) >> 3;
-      qoff[(size_t)k + 1] = qoff[(size_t)k] + 4 * ((col1 + 63) >> 6);
+    if (!reuse) {
+      std::vector<int64_t> qoff((size_t)nc + 1, 0);
+      for (int k = 0; k < nc; ++k) {
+        const int64_t col1 = ((int64_t)std::max(last[(size_t)k], 0) + 7) >> 3;
+        qoff[(size_t)k + 1] = qoff[(size_t)k] + 4 * ((col1 + 63) >> 6);
+      }
+      // (owned by the read set, not by the derived pool: a re-derivation keeps it)
+      if (!d->qoff_dev) {
+        void *qo = nullptr;
+        HIP_TRY(hipMalloc(&qo, sizeof(int64_t) * ((size_t)nc + 1)));
+        d->owned.push_back(qo);
+        d->qoff_dev = (int64_t *)qo;
+      }
+      HIP_TRY(hipMemcpyAsync(d->qoff_dev, qoff.data(), sizeof(int64_t) * ((size_t)nc + 1), hipMemcpyHostToDevice,
+                             c->stream));
+      if (lazy) HIP_TRY(hipStreamSynchronize(c->stream));  // (qoff is a local; the upload path waits below)
+      d->n_slices_kept = qoff[(size_t)nc];
+      d->pool_ordered_kept = unordered ? 0 : 1;
+      d->shape_kept = true;
     }
-    void *qo = nullptr;
-    HIP_TRY(d->dp.get(&qo, sizeof(int64_t) * ((size_t)nc + 1)));
-    HIP_TRY(hipMemcpyAsync(qo, qoff.data(), sizeof(int64_t) * ((size_t)nc + 1), hipMemcpyHostToDevice, c->stream));
-    d->d.qoff = (const int64_t *)qo;
-    d->n_slices = qoff[(size_t)nc];
-    const int64_t n_blk = qoff[(size_t)nc] / 4;
+    d->d.qoff = d->qoff_dev;
+    d->n_slices = d->n_slices_kept;
+    const int64_t n_blk = d->n_slices_kept / 4;
     void *bi = nullptr;
     HIP_TRY(d->dp.get(&bi, sizeof(int64_t) * 2 * (size_t)std::max<int64_t>(n_blk, 1)));
     int64_t *brb = (int64_t *)bi, *brs = brb + std::max<int64_t>(n_blk, 1);
@@ -2392,6 +2415,7 @@ void gq_reads_free(gq_dev_reads *d) {
       (void)hipEventDestroy(e);
     }
   for (void *p : d->owned) (void)hipFree(p);
+  if (d->vflag) (void)hipHostFree(d->vflag);
   d->dp.free_all();  // every derived structure, margin projection included
   delete d;
 }
@@ -2581,6 +2605,11 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
   gq_calls *res = (gq_calls *)calloc(1, sizeof(gq_calls));
   if (!res) return set_err(GQ_E_NOMEM, "calloc");
   if (pl.n_tiles == 0) {
+    st = validation_wait(rd);
+    if (st) {
+      free(res);
+      return st;
+    }
     *out = res;
     return GQ_OK;
   }
@@ -2606,10 +2635,16 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                            (int)(nbk + 1), c->stream));
   // ---- the finalize chain (record order, result image), sized from the device: see bucket_count
-  auto finalize = [&](Counters *ctr, size_t cap_rec) -> gq_status {
-    uint32_t *cnt = (uint32_t *)c->bkt.p, *off = cnt + (nbk + 1), *fill = off + (nbk + 1);
-    hipLaunchKernelGGL(zero_u32, dim3((unsigned)std::min<int64_t>((3 * (nbk + 1) + kBlock - 1) / kBlock, 1024)),
-                       dim3(kBlock), 0, c->stream, cnt, 3 * (nbk + 1));  // counts, (offsets), fills
+  // the chain's zero-initialised words live behind the counters, so the call's one memset of the
+  // counters clears them too: calls_image's chunk sums | bucket counts, (offsets), fills
+  const size_t fin_off = (sizeof(Counters) + 15) & ~(size_t)15;
+  const size_t fin_words = 2 * (size_t)kImgBlocks + 3 * (size_t)(nbk + 1);
+  auto finalize = [&](Counters *ctr, size_t cap_rec, bool cleared) -> gq_status {
+    unsigned long long *bsum = (unsigned long long *)((char *)ctr + fin_off);
+    uint32_t *cnt = (uint32_t *)(bsum + kImgBlocks), *off = cnt + (nbk + 1), *fill = off + (nbk + 1);
+    if (!cleared)  // (the chain a second time in one attempt, behind the re-runs)
+      hipLaunchKernelGGL(zero_u32, dim3((unsigned)std::min<int64_t>(((int64_t)fin_words + kBlock - 1) / kBlock, 1024)),
+                         dim3(kBlock), 0, c->stream, (uint32_t *)bsum, (int64_t)fin_words);
     const unsigned gb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)cap_rec + kBlock - 1) / kBlock, kFinBlocks));
     hipLaunchKernelGGL(bucket_count, dim3(gb), dim3(kBlock), 0, c->stream, (const CallRec *)c->recs.p,
                        ctr, og, dead_key, bshift, nbk, (uint64_t *)c->keys.p, (int32_t *)c->idx_sorted.p,
@@ -2623,12 +2658,10 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
                        (const int32_t *)c->keys_sorted.p, (const uint64_t *)c->keys.p, (const int32_t *)c->idx_sorted.p,
                        (const int64_t *)c->idx.p, (int32_t *)c->recs_sorted.p);
     HIP_TRY(hipGetLastError());
-    int64_t *bsum = (int64_t *)c->keys_sorted.p + (cap_rec + 1) / 2 + 1;  // past the members (int32)
     hipLaunchKernelGGL(img_sums, dim3(kImgBlocks), dim3(kBlock), 0, c->stream, (const CallRec *)c->recs.p,
                        (const int32_t *)c->recs_sorted.p, (const uint32_t *)off, nbk, bsum);
-    hipLaunchKernelGGL(img_scan, dim3(1), dim3(kImgBlocks), 0, c->stream, bsum);
     hipLaunchKernelGGL(calls_image, dim3(kImgBlocks), dim3(kBlock), 0, c->stream, (const CallRec *)c->recs.p,
-                       (const int32_t *)c->recs_sorted.p, (const uint32_t *)off, nbk, (const int64_t *)bsum,
+                       (const int32_t *)c->recs_sorted.p, (const uint32_t *)off, nbk, (const unsigned long long *)bsum,
                        (const uint8_t *)c->pool.p, ctr, (uint8_t *)c->image.p);
     HIP_TRY(hipGetLastError());
     return GQ_OK;
@@ -2647,18 +2680,17 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
     HIP_TRY(c->recs.ensure(cap_rec * sizeof(CallRec)));
     HIP_TRY(c->cplx.ensure(og.total(1) * sizeof(ComplexItem)));
     HIP_TRY(c->pool.ensure(pool_cap));
-    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    HIP_TRY(c->counters.ensure(fin_off + 4 * fin_words));
     // finalize buffers, by the record capacity (the chain never learns the count on the host)
     HIP_TRY(c->keys.ensure((cap_rec + 1) * 8));
-    HIP_TRY(c->keys_sorted.ensure((cap_rec + 1) * 4 + 8 * (kImgBlocks + 2) + 16));  // members | chunk sums
+    HIP_TRY(c->keys_sorted.ensure((cap_rec + 1) * 4));
     HIP_TRY(c->idx.ensure((cap_rec + 1) * 8));
     HIP_TRY(c->idx_sorted.ensure((cap_rec + 1) * 4));
     HIP_TRY(c->recs_sorted.ensure((cap_rec + 1) * 4));
-    HIP_TRY(c->bkt.ensure(sizeof(uint32_t) * (size_t)(3 * (nbk + 1))));
     HIP_TRY(c->sort_tmp.ensure(std::max<size_t>(scan_tmp, 16)));
     HIP_TRY(c->image.ensure(calls_layout((int64_t)cap_rec, (int64_t)pool_cap).bytes));
     Counters *ctr = (Counters *)c->counters.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipMemsetAsync(ctr, 0, fin_off + 4 * fin_words, c->stream));
     if (attempt == 0) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     st = launch_germline(c, pl.n_tiles, rd->d, p, (CallRec *)c->recs.p, (ComplexItem *)c->cplx.p, og, ctr, direct);
     if (st) {
@@ -2704,8 +2736,8 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
       free(res);
       return st;
     }
-    hipLaunchKernelGGL(part_scan, dim3(1), dim3(1024), 0, c->stream, ctr, 0, og);
-    {  // variant candidates -> records; unused slots get a key behind every ordinal
+    {  // variant candidates -> records; unused slots get a key behind every ordinal (and the
+       // records' partition offsets: its first workgroup is part_scan(ctr, 0))
 #ifndef GQ_EXPAND_BLOCKS
 #define GQ_EXPAND_BLOCKS 1024  // workgroups of germline_expand (each walks kParts / this many partitions)
 #endif
@@ -2715,13 +2747,14 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
     }
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     // the common case needs no re-run: order the records and build the image right away
-    st = finalize(ctr, cap_rec);
+    st = finalize(ctr, cap_rec, true);
     if (st) {
       free(res);
       return st;
     }
     HIP_TRY(hipEventRecord(c->ev[4], c->stream));
     st = read_counters(ctr);
+    if (!st) st = validation_settled(rd);  // (a re-derivation queued before this call: the stream has drained)
     if (st) {
       free(res);
       return st;
@@ -2810,7 +2843,7 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
         retry = true;
       }
       if (!retry) {
-        st = finalize(ctr, cap_rec);
+        st = finalize(ctr, cap_rec, false);
         if (!st) {
           HIP_TRY(hipEventRecord(c->ev[4], c->stream));
           st = read_counters(ctr);
@@ -2986,6 +3019,10 @@ void gq_free_calls(gq_calls *r) {
 gq_status gq_pileup_counts(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, gq_counts **out) {
   if (!c || !rd || !loci || !out) return set_err(GQ_E_ARG, "gq_pileup_counts: null argument");
   HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
   Plan pl;
   gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
   if (st) return st;
@@ -3082,6 +3119,10 @@ gq_status gq_vaf_histogram(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loc
   if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_vaf_histogram: null argument");
   if (p->bins < 1 || p->bins > 100) return set_err(GQ_E_ASSERT, "assumption failed: Bins should be between 1 and 100");
   HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
   memset(out, 0, sizeof(*out));
   Plan pl;
   gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)

@@ -1503,6 +1503,10 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
     return set_err(GQ_E_ARG, "tumor and normal read sets must share the contig list (%d vs %d contigs)",
                    t->d.n_contigs, n->d.n_contigs);
   const int dbg = getenv("GQ_DBG") ? atoi(getenv("GQ_DBG")) : 0;  // diagnostics only (read per call)
+  for (const gq_dev_reads *s : {t, n}) {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(s);
+    if (vs) return vs;
+  }
   RefView rv{nullptr, nullptr};
   std::vector<int32_t> lc;
   std::vector<int64_t> ls, le, lt;
@@ -1891,6 +1895,10 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
 gq_status gq_variant_support(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, gq_allele_counts **out) {
   if (!c || !rd || !loci || !out) return set_err(GQ_E_ARG, "gq_variant_support: null argument");
   HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -2071,6 +2079,10 @@ gq_status gq_germline_standard(gq_ctx *c, const gq_dev_reads *rd, const gq_loci 
                                gq_somatic_calls **out) {
   if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_germline_standard: null argument");
   HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -2264,6 +2276,10 @@ gq_status gq_allele_evidence(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *l
                              const gq_allele_evidence_params *p, gq_allele_evidence_rows **out) {
   if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_allele_evidence: null argument");
   HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
