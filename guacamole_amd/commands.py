@@ -801,6 +801,99 @@ def allele_evidence_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def genotype_likelihoods_reads(ctx: native.Context, rs: ReadSet, loci, **params) -> List[dict]:
+    """The log-likelihood of every diploid genotype over the eligible alleles of every sample's
+    pileup (Likelihood.likelihoodsOfAllPossibleGenotypesFromPileup, Likelihood.scala:99-201,
+    logSpace = true) at the loci pileupFlatMap(reads, partitions, skipEmpty=true) visits
+    (gq_genotype_likelihoods_call).  params: min_mapq (1), variants_only (True), include_alignment
+    (False), normalize (True).  Groups dict(contig (name), locus, sample (slot), depth, flags,
+    alleles=[(ref, alt, depth)], log_likelihoods=[...]), loci in call order, samples ascending."""
+    res = ctx.genotype_likelihoods(device_reads(ctx, rs), loci, **params)
+    groups = []
+    for g in res.groups:
+        g = dict(g)
+        g["contig"] = rs.contig_names[g["contig"]]
+        groups.append(g)
+    return groups
+
+
+GENOTYPE_LIKELIHOODS_HEADER = "contig,locus,sample,ref1,alt1,ref2,alt2,depth,alleleDepth1,alleleDepth2,logLikelihood,flags"
+
+
+def write_genotype_likelihoods_csv(path: str, groups: List[dict], sample_names: Sequence[str]) -> None:
+    """The groups of genotype_likelihoods_reads as CSV (GENOTYPE_LIKELIHOODS_HEADER), one line per
+    genotype: the sample by name, the log-likelihood as repr() writes it (it reads back to the same
+    bits), NaN as "NaN", the infinities as "Infinity" / "-Infinity".  Refuses an existing path."""
+    def num(x: float) -> str:
+        if x != x:
+            return "NaN"
+        if x in (float("inf"), float("-inf")):
+            return "Infinity" if x > 0 else "-Infinity"
+        return repr(x)
+    with open(path, "x") as fh:
+        fh.write(GENOTYPE_LIKELIHOODS_HEADER + "\n")
+        for g in groups:
+            s = g["sample"]
+            name = sample_names[s] if s < len(sample_names) else "default"
+            al, n = g["alleles"], len(g["alleles"])
+            head, tail = [g["contig"], str(g["locus"]), name], str(g["flags"])
+            k = 0
+            for i in range(n):
+                for j in range(i, n):
+                    fh.write(",".join(head + [al[i][0], al[i][1], al[j][0], al[j][1], str(g["depth"]), str(al[i][2]),
+                                              str(al[j][2]), num(g["log_likelihoods"][k]), tail]) + "\n")
+                    k += 1
+
+
+def genotype_likelihoods_main(argv: Sequence[str]) -> int:
+    """genotype-likelihoods: the log-likelihood of every diploid genotype at every variant locus
+    (--all-loci: at every visited locus) of one BAM, as CSV.  Input filters as germline-standard's
+    (GermlineStandardCaller.scala:53-54)."""
+    import os
+    p = argparse.ArgumentParser(prog="genotype-likelihoods",
+                                description="log-likelihood of every diploid genotype over the alleles at every "
+                                            "variant locus")
+    p.add_argument("--reads", required=True)
+    p.add_argument("--out", required=True, help="Output CSV path (must not exist)")
+    p.add_argument("--loci", default="", help="Loci to visit (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    p.add_argument("--min-mapq", type=int, default=1, help="Minimum read mapping quality for a read (Phred-scaled)")
+    p.add_argument("--all-loci", action="store_true", help="Every visited locus, not only those with a non-Match element")
+    p.add_argument("--include-alignment", action="store_true",
+                   help="Probability correct = base quality x mapping quality (somatic-standard's choice)")
+    p.add_argument("--raw", action="store_true", help="Log-likelihoods not normalized over the locus' genotypes")
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("genotype-likelihoods")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    builder = _loci_builder(args)
+    filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
+    ctx = None
+    rs = None
+    if device_ingest(args, args.reads):
+        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
+        ctx = native.Context(args.device)
+        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
+    if rs is None:
+        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    loci = builder.result(rs.contig_lengths_map)
+    parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
+    flat = flatten_partitions(parts, rs.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    groups = genotype_likelihoods_reads(ctx, rs, flat, min_mapq=args.min_mapq, variants_only=not args.all_loci,
+                                        include_alignment=args.include_alignment, normalize=not args.raw)
+    write_genotype_likelihoods_csv(args.out, groups, rs.sample_names)
+    print("Wrote %d genotype likelihoods of %d (locus, sample) groups." %
+          (sum(len(g["log_likelihoods"]) for g in groups), len(groups)), file=sys.stderr)
+    return 0
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -813,9 +906,9 @@ def warn_default_parallelism(args, world: int) -> None:
 
 
 def single_process_only(command: str) -> None:
-    """germline-standard, variant-support, vaf-histogram and allele-evidence run as one process on --device: under
-    torch.distributed.run every rank would repeat the whole job and write the same output, so a
-    multi-rank launch is refused."""
+    """germline-standard, variant-support, vaf-histogram, allele-evidence and genotype-likelihoods
+    run as one process on --device: under torch.distributed.run every rank would repeat the whole
+    job and write the same output, so a multi-rank launch is refused."""
     import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("%s runs as a single process (WORLD_SIZE=%s): launch it without torch.distributed.run "
@@ -838,7 +931,8 @@ def _finish_rank(rc: int) -> int:
 
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
-            "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main}
+            "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
+            "genotype-likelihoods": genotype_likelihoods_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -1254,6 +1254,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
 }
 
 #include "gq_allele_evidence.h"
+#include "gq_genotype_likelihoods.h"
 
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
   const int key = 2 * min_mapq + (incl_align ? 1 : 0);  // the projection's filter and probability model
@@ -2495,6 +2496,285 @@ void gq_free_allele_evidence(gq_allele_evidence_rows *r) {
   free(r->allele_pool);
   free(r->evidence);
   free(r->flags);
+  free(r);
+}
+
+namespace {
+GlLayout gl_layout(int64_t n_groups, int64_t n_alleles, int64_t n_geno, int64_t dev_pool_used) {
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t N = (size_t)n_groups, A = (size_t)n_alleles;
+  GlLayout L;
+  L.contig = 64;
+  L.pos = al(L.contig + 4 * N);
+  L.sample = al(L.pos + 8 * N);
+  L.depth = al(L.sample + 4 * N);
+  L.n_alleles = al(L.depth + 4 * N);
+  L.allele_first = al(L.n_alleles + 4 * N);
+  L.geno_first = al(L.allele_first + 8 * N);
+  L.flags = al(L.geno_first + 8 * N);
+  L.ref_off = al(L.flags + N);
+  L.ref_len = al(L.ref_off + 8 * A);
+  L.alt_off = al(L.ref_len + 4 * A);
+  L.alt_len = al(L.alt_off + 8 * A);
+  L.allele_depth = al(L.alt_len + 4 * A);
+  L.ll = al(L.allele_depth + 4 * A);
+  L.pool = al(L.ll + 8 * (size_t)n_geno);
+  // inline alleles hold <= 8 bytes; longer ones live in the device pool (each used once)
+  L.bytes = al(L.pool + 8 * A + (size_t)dev_pool_used + 1);
+  return L;
+}
+// The call into `res` (zeroed; the caller frees it, block included, when this fails).
+gq_status genotype_likelihoods_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                                   const gq_genotype_likelihood_params *p, gq_genotype_likelihoods *res) {
+  const auto h0 = std::chrono::steady_clock::now();
+  c->timings = gq_timings{};
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  Plan pl;
+  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
+  if (st) return st;
+  st = plan(c, rd, loci, kAeT, pl, c->tiles);
+  if (st) return st;
+  if (pl.n_tiles == 0) return GQ_OK;
+  // a buffer that overflowed is grown to what the pass needed and the pass repeated; each buffer
+  // has its own budget of two growths (the heap-order pass can add to what the first one needed)
+  enum { B_ITEM, B_AMB, B_DEEP, B_ALLELE, B_LL, B_POOL, B_N };
+  int grown[B_N] = {};
+  bool spent = false;
+  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
+    if (need <= cap) return false;
+    if (++grown[which] > 2) spent = true;
+    cap = need + slack;
+    return true;
+  };
+  {  // the phred -> success probability table, as the callers fill it
+    double succ[256];
+    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  // pileup element order: each window's first visited locus and initial (heap-ordered) group
+  SomWin sw{};
+  st = build_somwin(c, pl, rd, rd, sw);
+  if (st) return st;
+  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+    c->n_cu = 256;
+  const gq_allele_evidence_params lp{p->min_mapq, p->variants_only};
+  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
+                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
+                     allele_cap = 0, ll_cap = 0, pool_cap = 1 << 16, amb_cap = 4096, deep_cap = 4096;
+  Counters hc{};
+  int64_t n_items = 0;
+  for (;;) {
+    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
+    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
+    HIP_TRY(c->pool.ensure(pool_cap));
+    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
+    Counters *ctr = (Counters *)c->counters.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    // the loci to process: allele-evidence's list
+    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
+                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)lp.min_mapq,
+                       (int)lp.variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hc.err) break;
+    if (grow(B_ITEM, item_cap, hc.n_complex, 1024)) {
+      if (spent) return set_err(GQ_E_CAPACITY, "genotype-likelihoods: locus list capacity retries exhausted");
+      continue;
+    }
+    n_items = (int64_t)hc.n_complex;
+    if (n_items == 0) break;
+    // a listed locus gives at most one group per sample; alleles and genotypes per group are
+    // guessed (a variant locus mostly holds 2 or 3 alleles) and grown on overflow
+    const unsigned long long group_cap = (unsigned long long)n_items * (unsigned long long)std::max(rd->d.n_samples, 1);
+    allele_cap = std::max(allele_cap, 4 * group_cap + 4096);
+    ll_cap = std::max(ll_cap, 8 * group_cap + 4096);
+    HIP_TRY(c->srecs.ensure(group_cap * sizeof(GlGroup)));
+    HIP_TRY(c->recs.ensure(allele_cap * sizeof(GlAllele)));
+    HIP_TRY(c->recs_sorted.ensure(ll_cap * sizeof(double)));
+    const GlOut go{(GlGroup *)c->srecs.p, group_cap, (GlAllele *)c->recs.p, allele_cap,
+                   (double *)c->recs_sorted.p, ll_cap, (uint8_t *)c->pool.p, pool_cap};
+    int64_t *dl = (int64_t *)c->deep_list.p;
+    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
+    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
+    // mode, its per-wave scratch sized from the deepest of them
+    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
+                        int64_t n_ain) -> gq_status {
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
+      if (nd <= 0 || hc.err) return GQ_OK;
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
+      const int64_t waves = std::min<int64_t>(nd, 256);
+      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
+      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
+      hipLaunchKernelGGL(genotype_likelihoods_call<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)),
+                         dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items,
+                         rd->d, *p, go, ctr, sw, aout, acap, ain, aref, n_ain, deep);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      return GQ_OK;
+    };
+    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
+    hipLaunchKernelGGL(genotype_likelihoods_call<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
+                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, go, ctr, sw,
+                       (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, fast);
+    HIP_TRY(hipGetLastError());
+    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
+    if (st) return st;
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    bool retry = grow(B_AMB, amb_cap, hc.n_amb, 1024);
+    retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
+    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
+      std::vector<AmbItem> amb((size_t)hc.n_amb);
+      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(c->amb_ref.ensure(amb.size()));
+      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
+      if (st) return st;
+      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
+      const int64_t from = (int64_t)hc.n_deep;
+      hipLaunchKernelGGL(genotype_likelihoods_call<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, go, ctr, sw,
+                         (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                         (const uint8_t *)c->amb_ref.p, (int64_t)amb.size(), fast);
+      HIP_TRY(hipGetLastError());
+      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
+      if (st) return st;
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+      retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
+    }
+    retry |= grow(B_ALLELE, allele_cap, hc.n_out, 4096);
+    retry |= grow(B_LL, ll_cap, hc.out_pool, 4096);
+    retry |= grow(B_POOL, pool_cap, hc.pool_used, 4096);
+    if (!retry || hc.err) break;
+    if (spent) return set_err(GQ_E_CAPACITY, "genotype-likelihoods: output capacity retries exhausted");
+  }
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  st = check_device_error(c, hc);
+  if (st) return st;
+  // ---- on the device: groups by key, counts scanned to offsets, every column placed; one copy
+  const int64_t ng = n_items > 0 ? (int64_t)hc.n_rec : 0;
+  const int64_t n_all = ng ? (int64_t)hc.n_out : 0, n_geno = ng ? (int64_t)hc.out_pool : 0;
+  const GlLayout lay = gl_layout(ng, n_all, n_geno, ng ? (int64_t)std::min<unsigned long long>(hc.pool_used, pool_cap) : 0);
+  HIP_TRY(c->image.ensure(lay.bytes));
+  if (ng > 0) {
+    const size_t nn = (size_t)ng;
+    HIP_TRY(c->keys.ensure(nn * 8));
+    HIP_TRY(c->keys_sorted.ensure(nn * 8));
+    HIP_TRY(c->idx.ensure(nn * 4));
+    HIP_TRY(c->idx_sorted.ensure(nn * 4));
+    HIP_TRY(c->cands.ensure(6 * nn * sizeof(int64_t)));
+    const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
+    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
+    int64_t *sc = (int64_t *)c->cands.p;  // (the candidates' buffer: no caller runs beside this one)
+    const Gl3 cnt{sc, sc + nn, sc + 2 * nn}, off{sc + 3 * nn, sc + 4 * nn, sc + 5 * nn};
+    hipLaunchKernelGGL(gl_keys, dim3(nb), dim3(kBlock), 0, c->stream, (const GlGroup *)c->srecs.p, ng, keys, slot);
+    HIP_TRY(hipGetLastError());
+    const uint64_t key_bound = ((uint64_t)pl.n_loci << 12) | 0xFFFu;
+    const int end_bit = 64 - __builtin_clzll(key_bound);
+    size_t tmp = 0, tmp2 = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.a, off.a, (int)ng, c->stream));
+    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
+                                               c->stream));
+    hipLaunchKernelGGL(gl_counts, dim3(nb), dim3(kBlock), 0, c->stream, (const GlGroup *)c->srecs.p,
+                       (const uint32_t *)order, ng, cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.a, off.a, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.g, off.g, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.p, off.p, (int)ng, c->stream));
+    const unsigned pb = (unsigned)std::min<int64_t>((ng + kSomWaves - 1) / kSomWaves, (int64_t)32 * c->n_cu);
+    hipLaunchKernelGGL(gl_place, dim3(pb), dim3(kBlock), 0, c->stream, (const GlGroup *)c->srecs.p,
+                       (const uint32_t *)order, off, (const GlAllele *)c->recs.p,
+                       (const double *)c->recs_sorted.p, (const uint8_t *)c->pool.p, ng, lay, (uint8_t *)c->image.p);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemsetAsync(c->image.p, 0, 64, c->stream));
+  }
+  HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+  uint8_t *blk = (uint8_t *)malloc(lay.bytes);
+  if (!blk) return set_err(GQ_E_NOMEM, "genotype-likelihoods result block of %zu bytes", lay.bytes);
+  res->block_ = blk;
+  HIP_TRY(hipMemcpyAsync(blk, c->image.p, lay.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const auto m0 = std::chrono::steady_clock::now();
+  res->n_groups = ng;
+  res->contig = (int32_t *)(blk + lay.contig);
+  res->pos = (int64_t *)(blk + lay.pos);
+  res->sample = (int32_t *)(blk + lay.sample);
+  res->depth = (int32_t *)(blk + lay.depth);
+  res->n_alleles = (int32_t *)(blk + lay.n_alleles);
+  res->allele_first = (int64_t *)(blk + lay.allele_first);
+  res->geno_first = (int64_t *)(blk + lay.geno_first);
+  res->flags = blk + lay.flags;
+  res->n_alleles_total = n_all;
+  res->ref_off = (int64_t *)(blk + lay.ref_off);
+  res->ref_len = (int32_t *)(blk + lay.ref_len);
+  res->alt_off = (int64_t *)(blk + lay.alt_off);
+  res->alt_len = (int32_t *)(blk + lay.alt_len);
+  res->allele_depth = (int32_t *)(blk + lay.allele_depth);
+  res->allele_pool = blk + lay.pool;
+  res->pool_len = ng > 0 ? *(const int64_t *)blk : 0;
+  res->n_genotypes = n_geno;
+  res->log_likelihood = (double *)(blk + lay.ll);
+  res->visited_loci = (int64_t)hc.visited;
+  res->listed_loci = n_items;
+  c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timings.pileup_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+  c->timings.complex_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
+  c->timings.finalize_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
+  c->timings.walk_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
+  c->timings.total_ms = ms;
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = pl.n_tiles;
+  c->timings.deep_loci = (int64_t)hc.n_deep;
+  c->timings.deep_max = (int64_t)hc.deep_max;
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  return GQ_OK;
+}
+}  // namespace
+
+// timings: pileup_ms the list kernel, complex_ms the call kernels, finalize_ms ordering and
+// placement, walk_ms the device-to-host copy of the block, marshal_ms the host time after it.
+gq_status gq_genotype_likelihoods_call(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                                       const gq_genotype_likelihood_params *p, gq_genotype_likelihoods **out) {
+  if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_genotype_likelihoods_call: null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
+  gq_genotype_likelihoods *res = (gq_genotype_likelihoods *)calloc(1, sizeof(gq_genotype_likelihoods));
+  if (!res) return set_err(GQ_E_NOMEM, "calloc");
+  const gq_status st = genotype_likelihoods_run(c, rd, loci, p, res);
+  if (st) {
+    gq_free_genotype_likelihoods(res);
+    return st;
+  }
+  *out = res;
+  return GQ_OK;
+}
+
+void gq_free_genotype_likelihoods(gq_genotype_likelihoods *r) {
+  if (!r) return;
+  free(r->block_);  // one block holds every array
   free(r);
 }
 

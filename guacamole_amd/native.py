@@ -79,6 +79,11 @@ class gq_allele_evidence_params(C.Structure):
     _fields_ = [("min_mapq", C.c_int32), ("variants_only", C.c_int32)]
 
 
+class gq_genotype_likelihood_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("variants_only", C.c_int32), ("include_alignment", C.c_int32),
+                ("normalize", C.c_int32)]
+
+
 class gq_vaf_params(C.Structure):
     _fields_ = [("bins", C.c_int32), ("min_read_depth", C.c_int32), ("min_vaf", C.c_int32)]
 
@@ -160,6 +165,17 @@ class gq_allele_evidence_rows(C.Structure):
                 ("flags", C.POINTER(C.c_uint8)), ("visited_loci", C.c_int64), ("listed_loci", C.c_int64)]
 
 
+class gq_genotype_likelihoods(C.Structure):
+    _fields_ = [("n_groups", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int64)),
+                ("sample", C.POINTER(C.c_int32)), ("depth", C.POINTER(C.c_int32)), ("n_alleles", C.POINTER(C.c_int32)),
+                ("allele_first", C.POINTER(C.c_int64)), ("geno_first", C.POINTER(C.c_int64)),
+                ("flags", C.POINTER(C.c_uint8)), ("n_alleles_total", C.c_int64), ("ref_off", C.POINTER(C.c_int64)),
+                ("ref_len", C.POINTER(C.c_int32)), ("alt_off", C.POINTER(C.c_int64)), ("alt_len", C.POINTER(C.c_int32)),
+                ("allele_depth", C.POINTER(C.c_int32)), ("allele_pool", C.POINTER(C.c_uint8)), ("pool_len", C.c_int64),
+                ("n_genotypes", C.c_int64), ("log_likelihood", C.POINTER(C.c_double)), ("visited_loci", C.c_int64),
+                ("listed_loci", C.c_int64), ("block_", C.c_void_p)]
+
+
 EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timings", "gq_set_tile", "gq_reads_upload",
             "gq_reads_wrap_device", "gq_reads_free", "gq_reads_rederive", "gq_germline_threshold", "gq_germline_threshold_device",
             "gq_free_calls", "gq_pileup_counts",
@@ -169,7 +185,8 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_bam_dev_n_contigs", "gq_bam_dev_contig_name", "gq_bam_dev_contig_length", "gq_bam_dev_scan",
             "gq_bam_dev_reads", "gq_reads_positions", "gq_reads_contig_begin", "gq_reads_download", "gq_bam_dev_map",
             "gq_bam_dev_load", "gq_bam_dev_map_ex", "gq_bam_dev_plan", "gq_bam_dev_plan_segments",
-            "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence")
+            "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
+            "gq_free_genotype_likelihoods")
 
 
 def lib():
@@ -187,7 +204,7 @@ def lib():
                   "gq_reads_rederive",
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
-                  "gq_germline_standard", "gq_allele_evidence"):
+                  "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call"):
             getattr(L, f).restype = C.c_int
         L.gq_germline_threshold.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_params),
                                             C.POINTER(C.POINTER(gq_calls))]
@@ -210,6 +227,11 @@ def lib():
                                          C.POINTER(C.POINTER(gq_allele_evidence_rows))]
         L.gq_free_allele_evidence.argtypes = [C.POINTER(gq_allele_evidence_rows)]
         L.gq_free_allele_evidence.restype = None
+        L.gq_genotype_likelihoods_call.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci),
+                                                   C.POINTER(gq_genotype_likelihood_params),
+                                                   C.POINTER(C.POINTER(gq_genotype_likelihoods))]
+        L.gq_free_genotype_likelihoods.argtypes = [C.POINTER(gq_genotype_likelihoods)]
+        L.gq_free_genotype_likelihoods.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -448,6 +470,21 @@ class Context:
             return AlleleEvidenceRows.from_struct(out.contents)
         finally:
             lib().gq_free_allele_evidence(out)
+
+    def genotype_likelihoods(self, reads: "DeviceReads", loci, min_mapq: int = 1, variants_only: bool = True,
+                             include_alignment: bool = False, normalize: bool = True) -> "GenotypeLikelihoods":
+        """gq_genotype_likelihoods_call: the log-likelihood of every diploid genotype over the eligible
+        alleles of every sample at the visited loci (variants_only: at the loci whose filtered
+        pileup holds a non-Match element)."""
+        L, keep = make_gq_loci(*loci)
+        prm = gq_genotype_likelihood_params(int(min_mapq), int(bool(variants_only)), int(bool(include_alignment)),
+                                            int(bool(normalize)))
+        out = C.POINTER(gq_genotype_likelihoods)()
+        _check(lib().gq_genotype_likelihoods_call(self.h, reads.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return GenotypeLikelihoods.from_struct(out.contents)
+        finally:
+            lib().gq_free_genotype_likelihoods(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:
@@ -759,4 +796,75 @@ class AlleleEvidenceRows:
                           for ct, ps, sm, ro, rl, ao, al, fl, e in
                           zip(L["contig"], L["pos"], L["sample"], L["ref_off"], L["ref_len"], L["alt_off"],
                               L["alt_len"], L["flags"], ev)]
+        return self._rows
+
+
+class GenotypeLikelihoods:
+    """gq_genotype_likelihoods_call's result in output order: numpy columns copied out of the
+    library's block (per group, per allele, per genotype), dicts built on first use of ``groups``
+    / ``rows``."""
+
+    GROUP_COLUMNS = ("contig", "pos", "sample", "depth", "n_alleles", "allele_first", "geno_first", "flags")
+    ALLELE_COLUMNS = ("ref_off", "ref_len", "alt_off", "alt_len", "allele_depth")
+
+    def __init__(self, cols: Dict[str, np.ndarray], pool: bytes, visited: int, listed: int):
+        self.cols, self.pool, self.visited_loci, self.listed_loci = cols, pool, visited, listed
+        self._groups: Optional[List[dict]] = None
+        self._rows: Optional[List[dict]] = None
+
+    @staticmethod
+    def from_struct(c: gq_genotype_likelihoods) -> "GenotypeLikelihoods":
+        def col(name: str, n: int) -> np.ndarray:
+            dt = np.dtype(getattr(c, name)._type_)
+            if not n:
+                return np.zeros(0, dt)
+            buf = (C.c_uint8 * (n * dt.itemsize)).from_address(C.cast(getattr(c, name), C.c_void_p).value)
+            return np.frombuffer(buf, dtype=dt, count=n).copy()
+        cols = {k: col(k, int(c.n_groups)) for k in GenotypeLikelihoods.GROUP_COLUMNS}
+        cols.update({k: col(k, int(c.n_alleles_total)) for k in GenotypeLikelihoods.ALLELE_COLUMNS})
+        cols["log_likelihood"] = col("log_likelihood", int(c.n_genotypes))
+        pool = C.string_at(c.allele_pool, c.pool_len) if c.pool_len else b""
+        return GenotypeLikelihoods(cols, pool, int(c.visited_loci), int(c.listed_loci))
+
+    def __len__(self) -> int:
+        return int(self.cols["pos"].shape[0])
+
+    @property
+    def n_alleles_total(self) -> int:
+        return int(self.cols["ref_off"].shape[0])
+
+    @property
+    def n_genotypes(self) -> int:
+        return int(self.cols["log_likelihood"].shape[0])
+
+    @property
+    def groups(self) -> List[dict]:
+        """dict(contig (index), locus, sample (slot), depth, flags, alleles=[(ref, alt, depth)] in
+        Allele order, log_likelihoods=[...] row-major over the allele pairs i <= j)."""
+        if self._groups is None:
+            c, pool = self.cols, self.pool
+            L = {k: c[k].tolist() for k in self.GROUP_COLUMNS + self.ALLELE_COLUMNS}
+            ll = c["log_likelihood"].tolist()
+            al = [(pool[ro:ro + rl].decode("latin-1"), pool[ao:ao + an].decode("latin-1"), d)
+                  for ro, rl, ao, an, d in zip(L["ref_off"], L["ref_len"], L["alt_off"], L["alt_len"], L["allele_depth"])]
+            self._groups = [dict(contig=ct, locus=ps, sample=sm, depth=dp, flags=fl, alleles=al[af:af + n],
+                                 log_likelihoods=ll[gf:gf + n * (n + 1) // 2])
+                            for ct, ps, sm, dp, n, af, gf, fl in
+                            zip(L["contig"], L["pos"], L["sample"], L["depth"], L["n_alleles"], L["allele_first"],
+                                L["geno_first"], L["flags"])]
+        return self._groups
+
+    @property
+    def rows(self) -> List[dict]:
+        """One dict per genotype: contig (index), locus, sample (slot), allele1 / allele2 = (ref,
+        alt, depth), depth, log_likelihood, flags."""
+        if self._rows is None:
+            rows = []
+            for g in self.groups:
+                al, n = g["alleles"], len(g["alleles"])
+                pairs = [(i, j) for i in range(n) for j in range(i, n)]
+                rows.extend(dict(contig=g["contig"], locus=g["locus"], sample=g["sample"], allele1=al[i], allele2=al[j],
+                                 depth=g["depth"], log_likelihood=v, flags=g["flags"])
+                            for (i, j), v in zip(pairs, g["log_likelihoods"]))
+            self._rows = rows
         return self._rows

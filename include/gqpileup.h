@@ -484,6 +484,46 @@ gq_status gq_allele_evidence(gq_ctx *ctx, const gq_dev_reads *reads, const gq_lo
                              const gq_allele_evidence_params *params, gq_allele_evidence_rows **out);
 void gq_free_allele_evidence(gq_allele_evidence_rows *rows);
 
+/* genotype-likelihoods: Likelihood.likelihoodsOfAllPossibleGenotypesFromPileup
+ * (likelihood/Likelihood.scala:99-201) with logSpace = true and prior 1, for every sample's
+ * pileup at the loci pileupFlatMap(reads, partitions, skipEmpty = true) visits: the values the
+ * Bayesian callers compute and reduce to one genotype.  The loci, the mapq filter, the reference
+ * base and variants_only are gq_allele_evidence's.  One group per (locus, sample present in the
+ * filtered pileup) that has an eligible allele: a distinct allele of the filtered pileup whose alt
+ * bases are all standard (:106).  A group of n eligible alleles, in Allele order, has the
+ * n (n + 1) / 2 genotypes (i <= j) row-major (:107-110); log_likelihood holds, per genotype, the
+ * Colt fold + log(1.0) - log(2) * depth (:185-187), less log(sum of exp) over the group's genotypes
+ * in that order when normalize is set (:191-193).  Very deep pileups underflow to -inf / NaN as
+ * the reference's do.  Groups: loci in call order, samples ascending.  Every array lives in one
+ * block (block_), filled by one device-to-host copy.                                          */
+typedef struct {
+  int32_t min_mapq;           /* keep elements with read mapq >= min_mapq; 0 keeps all */
+  int32_t variants_only;      /* 1: only loci with a non-Match element after the filter */
+  int32_t include_alignment;  /* 0: probabilityCorrectIgnoringAlignment, 1: ...IncludingAlignment */
+  int32_t normalize;          /* 1: normalized log-likelihoods */
+} gq_genotype_likelihood_params;
+typedef struct {
+  int64_t n_groups;            /* (locus, sample) groups                                  */
+  int32_t *contig; int64_t *pos; int32_t *sample;
+  int32_t *depth;              /* the sample's filtered pileup size                        */
+  int32_t *n_alleles;          /* eligible alleles n; the group has n(n+1)/2 genotypes     */
+  int64_t *allele_first, *geno_first;   /* into the allele columns / log_likelihood        */
+  uint8_t *flags;              /* bit0: reference base from heap order                     */
+  int64_t n_alleles_total;
+  int64_t *ref_off; int32_t *ref_len; int64_t *alt_off; int32_t *alt_len; int32_t *allele_depth;
+  uint8_t *allele_pool; int64_t pool_len;
+  int64_t n_genotypes; double *log_likelihood;
+  int64_t visited_loci, listed_loci;
+  void *block_;
+} gq_genotype_likelihoods;
+#ifdef __cplusplus
+static_assert(sizeof(gq_genotype_likelihood_params) == 16, "gq_genotype_likelihood_params layout");
+static_assert(sizeof(gq_genotype_likelihoods) == 176, "gq_genotype_likelihoods layout");
+#endif
+gq_status gq_genotype_likelihoods_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
+                                       const gq_genotype_likelihood_params *params, gq_genotype_likelihoods **out);
+void gq_free_genotype_likelihoods(gq_genotype_likelihoods *res);
+
 /* vaf-histogram: VAFHistogram.variantLociFromReads + generateVAFHistogram
  * (commands/VAFHistogram.scala:208-229, 188-196): at every visited locus whose pileup holds a
  * non-Match element (VariantLocus.apply, :31-37), VAF = (depth - referenceDepth).toFloat /
