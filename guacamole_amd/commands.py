@@ -894,6 +894,87 @@ def genotype_likelihoods_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def pileup_elements_reads(ctx: native.Context, rs: ReadSet, loci, **params) -> List[dict]:
+    """The pileup itself (pileup/Pileup.scala:49-132) at the loci pileupFlatMap(reads, partitions,
+    skipEmpty=true) visits (gq_pileup_elements_call).  params: min_mapq (1), variants_only (True).
+    Groups dict(contig (name), locus, ref_base, flags, alleles=[(ref, alt, depth)] in Allele order,
+    elements=[dict(read, sample, mapq, reverse, kind, allele, quality, read_position, cigar_index,
+    index_within)] in Pileup.elements order), loci in call order; read indexes rs."""
+    res = ctx.pileup_elements(device_reads(ctx, rs), loci, **params)
+    groups = []
+    for g in res.groups:
+        g = dict(g)
+        g["contig"] = rs.contig_names[g["contig"]]
+        groups.append(g)
+    return groups
+
+
+PILEUP_ELEMENTS_HEADER = ("contig,locus,refBase,sample,readIndex,strand,mapq,kind,ref,alt,quality,readPosition,"
+                          "cigarElementIndex,indexWithinCigarElement,flags")
+
+
+def write_pileup_elements_csv(path: str, groups: List[dict], sample_names: Sequence[str]) -> None:
+    """The groups of pileup_elements_reads as CSV (PILEUP_ELEMENTS_HEADER), one line per element in
+    Pileup.elements order: the sample by name, the strand as + / -, the element's allele as its ref
+    and alt bases.  Refuses an existing path."""
+    with open(path, "x") as fh:
+        fh.write(PILEUP_ELEMENTS_HEADER + "\n")
+        for g in groups:
+            head, tail, al = [g["contig"], str(g["locus"]), g["ref_base"]], str(g["flags"]), g["alleles"]
+            for e in g["elements"]:
+                s = e["sample"]
+                name = sample_names[s] if s < len(sample_names) else "default"
+                a = al[e["allele"]]
+                fh.write(",".join(head + [name, str(e["read"]), "-" if e["reverse"] else "+", str(e["mapq"]), e["kind"],
+                                          a[0], a[1], str(e["quality"]), str(e["read_position"]), str(e["cigar_index"]),
+                                          str(e["index_within"]), tail]) + "\n")
+
+
+def pileup_elements_main(argv: Sequence[str]) -> int:
+    """pileup-elements: every element of the pileup at every variant locus (--all-loci: at every
+    visited locus) of one BAM, as CSV.  Input filters as germline-standard's
+    (GermlineStandardCaller.scala:53-54)."""
+    import os
+    p = argparse.ArgumentParser(prog="pileup-elements",
+                                description="the pileup itself (read, strand, alignment kind, allele, quality, CIGAR "
+                                            "cursor of every element) at every variant locus")
+    p.add_argument("--reads", required=True)
+    p.add_argument("--out", required=True, help="Output CSV path (must not exist)")
+    p.add_argument("--loci", default="", help="Loci to visit (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    p.add_argument("--min-mapq", type=int, default=1, help="Minimum read mapping quality for a read (Phred-scaled)")
+    p.add_argument("--all-loci", action="store_true", help="Every visited locus, not only those with a non-Match element")
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("pileup-elements")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    builder = _loci_builder(args)
+    filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
+    ctx = None
+    rs = None
+    if device_ingest(args, args.reads):
+        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
+        ctx = native.Context(args.device)
+        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
+    if rs is None:
+        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    loci = builder.result(rs.contig_lengths_map)
+    parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
+    flat = flatten_partitions(parts, rs.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    groups = pileup_elements_reads(ctx, rs, flat, min_mapq=args.min_mapq, variants_only=not args.all_loci)
+    write_pileup_elements_csv(args.out, groups, rs.sample_names)
+    print("Wrote %d pileup elements of %d loci." % (sum(len(g["elements"]) for g in groups), len(groups)),
+          file=sys.stderr)
+    return 0
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -906,8 +987,8 @@ def warn_default_parallelism(args, world: int) -> None:
 
 
 def single_process_only(command: str) -> None:
-    """germline-standard, variant-support, vaf-histogram, allele-evidence and genotype-likelihoods
-    run as one process on --device: under torch.distributed.run every rank would repeat the whole
+    """germline-standard, variant-support, vaf-histogram, allele-evidence, genotype-likelihoods and
+    pileup-elements run as one process on --device: under torch.distributed.run every rank would repeat the whole
     job and write the same output, so a multi-rank launch is refused."""
     import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -932,7 +1013,7 @@ def _finish_rank(rc: int) -> int:
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
-            "genotype-likelihoods": genotype_likelihoods_main}
+            "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

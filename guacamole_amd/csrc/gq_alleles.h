@@ -197,9 +197,10 @@ __device__ __forceinline__ int md_ref_at(const DevReads &R, int64_t r, int32_t p
 // Locate the PileupElement of read r at `pos` (PileupElement.apply + advanceToLocus) and
 // classify it (PileupElement.alignment).  Returns false and sets *errc on a reference error.
 // With mdv != nullptr the same CIGAR walk also yields md_ref_at(R, r, pos) in *mdv (always
-// set, also when classify fails).
+// set, also when classify fails).  With cur != nullptr it yields the element's cursor
+// (PileupElement.readPosition, cigarElementIndex, indexWithinCigarElement) in cur[0..3).
 __device__ __forceinline__ bool classify(const DevReads &R, int64_t r, int32_t pos, uint8_t refbase, AlleleDesc &d, int *errc,
-                                         int *mdv = nullptr) {
+                                         int *mdv = nullptr, int32_t *cur = nullptr) {
   const int32_t s = R.start[r];
   const int64_t cig_off = R.cigar_off[r];
   const int32_t ncig = R.n_cigar[r];
@@ -235,6 +236,11 @@ __device__ __forceinline__ bool classify(const DevReads &R, int64_t r, int32_t p
   const uint32_t c = R.cigar[cig_off + ci];
   const int op = (int)(c & 15u);
   const int32_t len = (int32_t)(c >> 4);
+  if (cur) {
+    cur[0] = rp;
+    cur[1] = ci;
+    cur[2] = within;
+  }
   if (mdv) {  // md_ref_at's answer from this walk (rp is the read offset at pos in a read op)
     if (op == OP_I) {
       *mdv = md_ref_at(R, r, pos);  // (pos 0 behind a leading insertion)

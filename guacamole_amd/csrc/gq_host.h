@@ -984,7 +984,7 @@ struct DevBuf {
 struct gq_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {};
+  hipEvent_t ev[7] = {};
   hipEvent_t dev_ev[4] = {};  // the derivation's device spans (gq_reads_info: derive / projection / fill)
   // a second stream for derivation kernels independent of the main stream's (the pool scan beside
   // the read checks, the sparse entries beside the projection fill), joined by side_ev

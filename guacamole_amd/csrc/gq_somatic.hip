@@ -1255,6 +1255,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
 
 #include "gq_allele_evidence.h"
 #include "gq_genotype_likelihoods.h"
+#include "gq_pileup_elements.h"
 
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
   const int key = 2 * min_mapq + (incl_align ? 1 : 0);  // the projection's filter and probability model
@@ -2773,6 +2774,310 @@ gq_status gq_genotype_likelihoods_call(gq_ctx *c, const gq_dev_reads *rd, const 
 }
 
 void gq_free_genotype_likelihoods(gq_genotype_likelihoods *r) {
+  if (!r) return;
+  free(r->block_);  // one block holds every array
+  free(r);
+}
+
+namespace {
+PeLayout pe_layout(int64_t n_groups, int64_t n_alleles, int64_t n_elems, int64_t pool_bytes) {
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t N = (size_t)n_groups, A = (size_t)n_alleles, E = (size_t)n_elems;
+  PeLayout L;
+  L.contig = 0;
+  L.pos = al(L.contig + 4 * N);
+  L.ref_base = al(L.pos + 8 * N);
+  L.flags = al(L.ref_base + N);
+  L.depth = al(L.flags + N);
+  L.n_alleles = al(L.depth + 4 * N);
+  L.elem_first = al(L.n_alleles + 4 * N);
+  L.allele_first = al(L.elem_first + 8 * N);
+  L.ref_off = al(L.allele_first + 8 * N);
+  L.ref_len = al(L.ref_off + 8 * A);
+  L.alt_off = al(L.ref_len + 4 * A);
+  L.alt_len = al(L.alt_off + 8 * A);
+  L.allele_depth = al(L.alt_len + 4 * A);
+  L.e_read = al(L.allele_depth + 4 * A);
+  L.e_sample = al(L.e_read + 8 * E);
+  L.e_mapq = al(L.e_sample + E);
+  L.e_strand = al(L.e_mapq + E);
+  L.e_kind = al(L.e_strand + E);
+  L.e_allele = al(L.e_kind + E);
+  L.e_quality = al(L.e_allele + 4 * E);
+  L.e_rpos = al(L.e_quality + 2 * E);
+  L.e_cigar = al(L.e_rpos + 4 * E);
+  L.e_within = al(L.e_cigar + 4 * E);
+  L.pool = al(L.e_within + 4 * E);
+  L.bytes = al(L.pool + (size_t)pool_bytes + 1);
+  return L;
+}
+// The call into `res` (zeroed; the caller frees it, block included, when this fails).
+gq_status pileup_elements_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                              const gq_pileup_elements_params *p, gq_pileup_elements *res) {
+  const auto h0 = std::chrono::steady_clock::now();
+  c->timings = gq_timings{};
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  Plan pl;
+  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
+  if (st) return st;
+  st = plan(c, rd, loci, kAeT, pl, c->tiles);
+  if (st) return st;
+  if (pl.n_tiles == 0) return GQ_OK;
+  // a buffer that overflowed is grown to what the pass needed and the pass repeated; each buffer
+  // has its own budget of two growths (the heap-order pass can add to what the first one needed)
+  enum { B_ITEM, B_AMB, B_DEEP, B_N };
+  int grown[B_N] = {};
+  bool spent = false;
+  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
+    if (need <= cap) return false;
+    if (++grown[which] > 2) spent = true;
+    cap = need + slack;
+    return true;
+  };
+  // pileup element order: each window's first visited locus and initial (heap-ordered) group
+  SomWin sw{};
+  st = build_somwin(c, pl, rd, rd, sw);
+  if (st) return st;
+  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+    c->n_cu = 256;
+  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
+                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
+                     amb_cap = 4096, deep_cap = 4096;
+  Counters hc{};
+  Counters *ctr = nullptr;
+  int64_t n_items = 0;
+  for (;;) {
+    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
+    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
+    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
+    ctr = (Counters *)c->counters.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    // the loci to process: allele-evidence's list
+    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
+                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)p->min_mapq,
+                       (int)p->variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hc.err) break;
+    if (grow(B_ITEM, item_cap, hc.n_complex, 1024)) {
+      if (spent) return set_err(GQ_E_CAPACITY, "pileup-elements: locus list capacity retries exhausted");
+      continue;
+    }
+    n_items = (int64_t)hc.n_complex;
+    if (n_items == 0) break;
+    // the size pass: one record per listed locus at most
+    const unsigned long long rec_cap = (unsigned long long)n_items;
+    HIP_TRY(c->srecs.ensure(rec_cap * sizeof(PeRec)));
+    PeRec *recs = (PeRec *)c->srecs.p;
+    int64_t *dl = (int64_t *)c->deep_list.p;
+    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
+    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
+    // mode, its per-wave scratch sized from the deepest of them
+    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
+                        int64_t n_ain) -> gq_status {
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
+      if (nd <= 0 || hc.err) return GQ_OK;
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
+      const int64_t waves = std::min<int64_t>(nd, 256);
+      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
+      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
+      hipLaunchKernelGGL(pileup_elements_size<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)),
+                         dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items,
+                         rd->d, *p, recs, rec_cap, ctr, sw, aout, acap, ain, aref, n_ain, deep);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      return GQ_OK;
+    };
+    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
+    hipLaunchKernelGGL(pileup_elements_size<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
+                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, recs, rec_cap, ctr,
+                       sw, (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0,
+                       fast);
+    HIP_TRY(hipGetLastError());
+    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
+    if (st) return st;
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    bool retry = grow(B_AMB, amb_cap, hc.n_amb, 1024);
+    retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
+    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
+      std::vector<AmbItem> amb((size_t)hc.n_amb);
+      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(c->amb_ref.ensure(amb.size()));
+      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
+      if (st) return st;
+      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
+      const int64_t from = (int64_t)hc.n_deep;
+      hipLaunchKernelGGL(pileup_elements_size<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, recs, rec_cap, ctr,
+                         sw, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                         (const uint8_t *)c->amb_ref.p, (int64_t)amb.size(), fast);
+      HIP_TRY(hipGetLastError());
+      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
+      if (st) return st;
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+      retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
+    }
+    if (!retry || hc.err) break;
+    if (spent) return set_err(GQ_E_CAPACITY, "pileup-elements: list capacity retries exhausted");
+  }
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  const int64_t visited = (int64_t)hc.visited;
+  st = check_device_error(c, hc);
+  if (st) return st;
+  // ---- on the device: the records by call order, their three sizes scanned to offsets, then the
+  // fill pass writes every column of the result image; one copy
+  const int64_t ng = n_items > 0 ? (int64_t)hc.n_rec : 0;
+  const int64_t n_el = ng ? (int64_t)hc.n_out : 0, n_all = ng ? (int64_t)hc.out_pool : 0,
+                n_pool = ng ? (int64_t)hc.pool_used : 0;
+  const PeLayout lay = pe_layout(ng, n_all, n_el, n_pool);
+  HIP_TRY(c->image.ensure(lay.bytes));
+  if (ng > 0) {
+    const size_t nn = (size_t)ng;
+    HIP_TRY(c->keys.ensure(nn * 8));
+    HIP_TRY(c->keys_sorted.ensure(nn * 8));
+    HIP_TRY(c->idx.ensure(nn * 4));
+    HIP_TRY(c->idx_sorted.ensure(nn * 4));
+    HIP_TRY(c->cands.ensure(6 * nn * sizeof(int64_t)));
+    const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
+    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
+    int64_t *sc = (int64_t *)c->cands.p;  // (the candidates' buffer: no caller runs beside this one)
+    const Pe3 cnt{sc, sc + nn, sc + 2 * nn}, off{sc + 3 * nn, sc + 4 * nn, sc + 5 * nn};
+    const PeRec *recs = (const PeRec *)c->srecs.p;
+    hipLaunchKernelGGL(pe_keys, dim3(nb), dim3(kBlock), 0, c->stream, recs, ng, keys, slot);
+    HIP_TRY(hipGetLastError());
+    const uint64_t key_bound = (uint64_t)pl.n_loci;
+    const int end_bit = std::max(1, 64 - __builtin_clzll(key_bound | 1ull));
+    size_t tmp = 0, tmp2 = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.a, off.a, (int)ng, c->stream));
+    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
+                                               c->stream));
+    hipLaunchKernelGGL(pe_counts, dim3(nb), dim3(kBlock), 0, c->stream, recs, (const uint32_t *)order, ng, cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.e, off.e, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.a, off.a, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.p, off.p, (int)ng, c->stream));
+    HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+    const unsigned fb = (unsigned)std::min<int64_t>((ng + kSomWaves - 1) / kSomWaves, 8192);
+    hipLaunchKernelGGL(pileup_elements_fill<false>, dim3(fb), dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p,
+                       (const ComplexItem *)c->cplx.p, rd->d, (int)p->min_mapq, recs, (const uint32_t *)order, ng, off, lay,
+                       (uint8_t *)c->image.p, ctr, sw, DeepSel{nullptr, 0, nullptr, 0, nullptr, 0, 0});
+    HIP_TRY(hipGetLastError());
+    if (hc.n_deep > 0) {  // the deep size pass' groups: the same scratch geometry, a slice per launched wave
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
+      const int64_t dblocks = (std::min<int64_t>((int64_t)hc.n_deep, 256) + kSomWaves - 1) / kSomWaves;
+      HIP_TRY(c->deep_scratch.ensure((size_t)(dblocks * kSomWaves) * gs_wave_bytes(scap, 16) + 256));
+      hipLaunchKernelGGL(pileup_elements_fill<true>, dim3((unsigned)dblocks), dim3(kBlock), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, rd->d, (int)p->min_mapq, recs,
+                         (const uint32_t *)order, ng, off, lay, (uint8_t *)c->image.p, ctr, sw,
+                         DeepSel{nullptr, 0, nullptr, 0, (uint8_t *)c->deep_scratch.p, scap, 16});
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));  // (the fill pass' errors)
+  } else {
+    HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+  }
+  HIP_TRY(hipEventRecord(c->ev[6], c->stream));
+  uint8_t *blk = (uint8_t *)malloc(lay.bytes);
+  if (!blk) return set_err(GQ_E_NOMEM, "pileup-elements result block of %zu bytes", lay.bytes);
+  res->block_ = blk;
+  if (ng > 0) HIP_TRY(hipMemcpyAsync(blk, c->image.p, lay.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (ng > 0) {
+    st = check_device_error(c, hc);
+    if (st) return st;
+  }
+  const auto m0 = std::chrono::steady_clock::now();
+  res->n_groups = ng;
+  res->contig = (int32_t *)(blk + lay.contig);
+  res->pos = (int64_t *)(blk + lay.pos);
+  res->ref_base = blk + lay.ref_base;
+  res->flags = blk + lay.flags;
+  res->depth = (int32_t *)(blk + lay.depth);
+  res->n_alleles = (int32_t *)(blk + lay.n_alleles);
+  res->elem_first = (int64_t *)(blk + lay.elem_first);
+  res->allele_first = (int64_t *)(blk + lay.allele_first);
+  res->n_alleles_total = n_all;
+  res->ref_off = (int64_t *)(blk + lay.ref_off);
+  res->ref_len = (int32_t *)(blk + lay.ref_len);
+  res->alt_off = (int64_t *)(blk + lay.alt_off);
+  res->alt_len = (int32_t *)(blk + lay.alt_len);
+  res->allele_depth = (int32_t *)(blk + lay.allele_depth);
+  res->allele_pool = blk + lay.pool;
+  res->pool_len = n_pool;
+  res->n_elements = n_el;
+  res->elem_read = (int64_t *)(blk + lay.e_read);
+  res->elem_sample = blk + lay.e_sample;
+  res->elem_mapq = blk + lay.e_mapq;
+  res->elem_strand = blk + lay.e_strand;
+  res->elem_kind = blk + lay.e_kind;
+  res->elem_allele = (int32_t *)(blk + lay.e_allele);
+  res->elem_quality = (int16_t *)(blk + lay.e_quality);
+  res->elem_read_position = (int32_t *)(blk + lay.e_rpos);
+  res->elem_cigar_index = (int32_t *)(blk + lay.e_cigar);
+  res->elem_index_within = (int32_t *)(blk + lay.e_within);
+  res->visited_loci = visited;
+  res->listed_loci = n_items;
+  res->block_bytes = (int64_t)lay.bytes;
+  c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timings.pileup_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+  c->timings.complex_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
+  c->timings.finalize_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
+  c->timings.call_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[6], c->ev[4]);
+  c->timings.walk_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
+  c->timings.total_ms = ms;
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = pl.n_tiles;
+  c->timings.deep_loci = (int64_t)hc.n_deep;
+  c->timings.deep_max = (int64_t)hc.deep_max;
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  return GQ_OK;
+}
+}  // namespace
+
+// timings: pileup_ms the list kernel, complex_ms the size pass (heap-order round trip included),
+// finalize_ms ordering and scans, call_ms the fill pass, walk_ms the device-to-host copy of the
+// block, marshal_ms the host time after it.
+gq_status gq_pileup_elements_call(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                                  const gq_pileup_elements_params *p, gq_pileup_elements **out) {
+  if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_pileup_elements_call: null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
+  gq_pileup_elements *res = (gq_pileup_elements *)calloc(1, sizeof(gq_pileup_elements));
+  if (!res) return set_err(GQ_E_NOMEM, "calloc");
+  const gq_status st = pileup_elements_run(c, rd, loci, p, res);
+  if (st) {
+    gq_free_pileup_elements(res);
+    return st;
+  }
+  *out = res;
+  return GQ_OK;
+}
+
+void gq_free_pileup_elements(gq_pileup_elements *r) {
   if (!r) return;
   free(r->block_);  // one block holds every array
   free(r);

@@ -176,6 +176,30 @@ class gq_genotype_likelihoods(C.Structure):
                 ("listed_loci", C.c_int64), ("block_", C.c_void_p)]
 
 
+class gq_pileup_elements_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("variants_only", C.c_int32)]
+
+
+class gq_pileup_elements(C.Structure):
+    _fields_ = [("n_groups", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int64)),
+                ("ref_base", C.POINTER(C.c_uint8)), ("flags", C.POINTER(C.c_uint8)), ("depth", C.POINTER(C.c_int32)),
+                ("n_alleles", C.POINTER(C.c_int32)), ("elem_first", C.POINTER(C.c_int64)),
+                ("allele_first", C.POINTER(C.c_int64)), ("n_alleles_total", C.c_int64),
+                ("ref_off", C.POINTER(C.c_int64)), ("ref_len", C.POINTER(C.c_int32)), ("alt_off", C.POINTER(C.c_int64)),
+                ("alt_len", C.POINTER(C.c_int32)), ("allele_depth", C.POINTER(C.c_int32)),
+                ("allele_pool", C.POINTER(C.c_uint8)), ("pool_len", C.c_int64), ("n_elements", C.c_int64),
+                ("elem_read", C.POINTER(C.c_int64)), ("elem_sample", C.POINTER(C.c_uint8)),
+                ("elem_mapq", C.POINTER(C.c_uint8)), ("elem_strand", C.POINTER(C.c_uint8)),
+                ("elem_kind", C.POINTER(C.c_uint8)), ("elem_allele", C.POINTER(C.c_int32)),
+                ("elem_quality", C.POINTER(C.c_int16)), ("elem_read_position", C.POINTER(C.c_int32)),
+                ("elem_cigar_index", C.POINTER(C.c_int32)), ("elem_index_within", C.POINTER(C.c_int32)),
+                ("visited_loci", C.c_int64), ("listed_loci", C.c_int64), ("block_bytes", C.c_int64),
+                ("block_", C.c_void_p)]
+
+
+# gq_pileup_elements.elem_kind (PileupElement.alignment)
+ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
+
 EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timings", "gq_set_tile", "gq_reads_upload",
             "gq_reads_wrap_device", "gq_reads_free", "gq_reads_rederive", "gq_germline_threshold", "gq_germline_threshold_device",
             "gq_free_calls", "gq_pileup_counts",
@@ -186,7 +210,7 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_bam_dev_reads", "gq_reads_positions", "gq_reads_contig_begin", "gq_reads_download", "gq_bam_dev_map",
             "gq_bam_dev_load", "gq_bam_dev_map_ex", "gq_bam_dev_plan", "gq_bam_dev_plan_segments",
             "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
-            "gq_free_genotype_likelihoods")
+            "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements")
 
 
 def lib():
@@ -204,7 +228,8 @@ def lib():
                   "gq_reads_rederive",
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
-                  "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call"):
+                  "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call",
+                  "gq_pileup_elements_call"):
             getattr(L, f).restype = C.c_int
         L.gq_germline_threshold.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_params),
                                             C.POINTER(C.POINTER(gq_calls))]
@@ -232,6 +257,11 @@ def lib():
                                                    C.POINTER(C.POINTER(gq_genotype_likelihoods))]
         L.gq_free_genotype_likelihoods.argtypes = [C.POINTER(gq_genotype_likelihoods)]
         L.gq_free_genotype_likelihoods.restype = None
+        L.gq_pileup_elements_call.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci),
+                                              C.POINTER(gq_pileup_elements_params),
+                                              C.POINTER(C.POINTER(gq_pileup_elements))]
+        L.gq_free_pileup_elements.argtypes = [C.POINTER(gq_pileup_elements)]
+        L.gq_free_pileup_elements.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -485,6 +515,20 @@ class Context:
             return GenotypeLikelihoods.from_struct(out.contents)
         finally:
             lib().gq_free_genotype_likelihoods(out)
+
+    def pileup_elements(self, reads: "DeviceReads", loci, min_mapq: int = 1,
+                        variants_only: bool = True) -> "PileupElements":
+        """gq_pileup_elements_call: every kept element of every visited locus' pileup in
+        Pileup.elements order, with the locus' distinct alleles (variants_only: at the loci whose
+        filtered pileup holds a non-Match element)."""
+        L, keep = make_gq_loci(*loci)
+        prm = gq_pileup_elements_params(int(min_mapq), int(bool(variants_only)))
+        out = C.POINTER(gq_pileup_elements)()
+        _check(lib().gq_pileup_elements_call(self.h, reads.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return PileupElements.from_struct(out.contents)
+        finally:
+            lib().gq_free_pileup_elements(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:
@@ -868,3 +912,70 @@ class GenotypeLikelihoods:
                             for (i, j), v in zip(pairs, g["log_likelihoods"]))
             self._rows = rows
         return self._rows
+
+
+class PileupElements:
+    """gq_pileup_elements_call's result in output order: numpy columns copied out of the library's
+    block (per group = locus, per allele, per element), dicts built on first use of ``groups``."""
+
+    GROUP_COLUMNS = ("contig", "pos", "ref_base", "flags", "depth", "n_alleles", "elem_first", "allele_first")
+    ALLELE_COLUMNS = ("ref_off", "ref_len", "alt_off", "alt_len", "allele_depth")
+    ELEMENT_COLUMNS = ("elem_read", "elem_sample", "elem_mapq", "elem_strand", "elem_kind", "elem_allele",
+                       "elem_quality", "elem_read_position", "elem_cigar_index", "elem_index_within")
+
+    def __init__(self, cols: Dict[str, np.ndarray], pool: bytes, visited: int, listed: int, block_bytes: int = 0):
+        self.cols, self.pool, self.visited_loci, self.listed_loci = cols, pool, visited, listed
+        self.block_bytes = block_bytes
+        self._groups: Optional[List[dict]] = None
+
+    @staticmethod
+    def from_struct(c: gq_pileup_elements) -> "PileupElements":
+        def col(name: str, n: int) -> np.ndarray:
+            dt = np.dtype(getattr(c, name)._type_)
+            if not n:
+                return np.zeros(0, dt)
+            buf = (C.c_uint8 * (n * dt.itemsize)).from_address(C.cast(getattr(c, name), C.c_void_p).value)
+            return np.frombuffer(buf, dtype=dt, count=n).copy()
+        cols = {k: col(k, int(c.n_groups)) for k in PileupElements.GROUP_COLUMNS}
+        cols.update({k: col(k, int(c.n_alleles_total)) for k in PileupElements.ALLELE_COLUMNS})
+        cols.update({k: col(k, int(c.n_elements)) for k in PileupElements.ELEMENT_COLUMNS})
+        pool = C.string_at(c.allele_pool, c.pool_len) if c.pool_len else b""
+        return PileupElements(cols, pool, int(c.visited_loci), int(c.listed_loci), int(c.block_bytes))
+
+    def __len__(self) -> int:
+        return int(self.cols["pos"].shape[0])
+
+    @property
+    def n_loci(self) -> int:
+        return len(self)
+
+    @property
+    def n_alleles_total(self) -> int:
+        return int(self.cols["ref_off"].shape[0])
+
+    @property
+    def n_elements(self) -> int:
+        return int(self.cols["elem_read"].shape[0])
+
+    @property
+    def groups(self) -> List[dict]:
+        """dict(contig (index), locus, ref_base, flags, alleles=[(ref, alt, depth)] in Allele order,
+        elements=[dict(read, sample, mapq, reverse, kind, allele, quality, read_position, cigar_index,
+        index_within)] in Pileup.elements order; kind is one of ELEMENT_KINDS, allele indexes alleles."""
+        if self._groups is None:
+            c, pool = self.cols, self.pool
+            L = {k: c[k].tolist() for k in self.GROUP_COLUMNS + self.ALLELE_COLUMNS + self.ELEMENT_COLUMNS}
+            al = [(pool[ro:ro + rl].decode("latin-1"), pool[ao:ao + an].decode("latin-1"), d)
+                  for ro, rl, ao, an, d in zip(L["ref_off"], L["ref_len"], L["alt_off"], L["alt_len"], L["allele_depth"])]
+            el = [dict(read=rd, sample=sm, mapq=mq, reverse=bool(st), kind=ELEMENT_KINDS[kd], allele=a, quality=q,
+                       read_position=rp, cigar_index=ci, index_within=iw)
+                  for rd, sm, mq, st, kd, a, q, rp, ci, iw in
+                  zip(L["elem_read"], L["elem_sample"], L["elem_mapq"], L["elem_strand"], L["elem_kind"],
+                      L["elem_allele"], L["elem_quality"], L["elem_read_position"], L["elem_cigar_index"],
+                      L["elem_index_within"])]
+            self._groups = [dict(contig=ct, locus=ps, ref_base=chr(rb), flags=fl, alleles=al[af:af + na],
+                                 elements=el[ef:ef + dp])
+                            for ct, ps, rb, fl, dp, na, ef, af in
+                            zip(L["contig"], L["pos"], L["ref_base"], L["flags"], L["depth"], L["n_alleles"],
+                                L["elem_first"], L["allele_first"])]
+        return self._groups

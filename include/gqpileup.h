@@ -524,6 +524,62 @@ gq_status gq_genotype_likelihoods_call(gq_ctx *ctx, const gq_dev_reads *reads, c
                                        const gq_genotype_likelihood_params *params, gq_genotype_likelihoods **out);
 void gq_free_genotype_likelihoods(gq_genotype_likelihoods *res);
 
+/* pileup-elements: the Pileup itself (pileup/Pileup.scala:49-132, pileup/PileupElement.scala) at
+ * the loci pileupFlatMap(reads, partitions, skipEmpty = true) visits: the general case of a
+ * per-locus callback, which a host runs over the flat arrays below.  The loci, the mapq filter,
+ * the reference base, variants_only and the flag bit are gq_allele_evidence's.  One group per
+ * locus whose filtered pileup is not empty, in call order.  A group holds
+ *   - its kept elements [elem_first, elem_first + depth) in Pileup.elements order: the task
+ *     window's initial-group reads still covering the locus in currentRegions() heap order, then
+ *     the other covering reads in read order (the filter removes elements without reordering;
+ *     Pileup.bySample is a stable filter on elem_sample);
+ *   - its distinct alleles [allele_first, allele_first + n_alleles) over the kept elements, in
+ *     Allele order (ref bytes, then alt bytes), with each one's element count.
+ * Every array lives in one block (block_), filled by one device-to-host copy.                  */
+typedef struct {
+  int32_t min_mapq;        /* keep elements with read mapq >= min_mapq; 0 keeps all */
+  int32_t variants_only;   /* 1: only loci with a non-Match element after the filter */
+} gq_pileup_elements_params;
+/* elem_kind: PileupElement.alignment against the pileup's reference base */
+enum { GQ_ELEM_MATCH = 0, GQ_ELEM_MISMATCH = 1, GQ_ELEM_INSERTION = 2, GQ_ELEM_DELETION = 3,
+       GQ_ELEM_MIDDELETION = 4, GQ_ELEM_CLIPPED = 5 };
+typedef struct {
+  int64_t n_groups;            /* loci                                                     */
+  int32_t *contig; int64_t *pos;
+  uint8_t *ref_base;           /* the (unfiltered) pileup's reference base                 */
+  uint8_t *flags;              /* bit0: reference base from heap order                     */
+  int32_t *depth;              /* kept elements                                            */
+  int32_t *n_alleles;          /* distinct alleles of the kept elements                    */
+  int64_t *elem_first, *allele_first;   /* into the element / allele columns               */
+  int64_t n_alleles_total;
+  int64_t *ref_off; int32_t *ref_len; int64_t *alt_off; int32_t *alt_len;   /* into allele_pool */
+  int32_t *allele_depth;       /* kept elements with this allele                           */
+  uint8_t *allele_pool; int64_t pool_len;
+  int64_t n_elements;
+  int64_t *elem_read;          /* index into the resident read set (gq_reads_download's numbering) */
+  uint8_t *elem_sample;        /* the read's sample slot                                   */
+  uint8_t *elem_mapq;
+  uint8_t *elem_strand;        /* 1: reverse strand                                        */
+  uint8_t *elem_kind;          /* GQ_ELEM_*                                                */
+  int32_t *elem_allele;        /* index into the group's alleles (allele_first + ...)      */
+  int16_t *elem_quality;       /* PileupElement.qualityScore: the (signed) base quality, the */
+                               /* minimum over an insertion's bases, the read's mapq for   */
+                               /* MidDeletion / Clipped                                    */
+  int32_t *elem_read_position; /* PileupElement.readPosition                               */
+  int32_t *elem_cigar_index;   /* PileupElement.cigarElementIndex                          */
+  int32_t *elem_index_within;  /* PileupElement.indexWithinCigarElement                    */
+  int64_t visited_loci, listed_loci;
+  int64_t block_bytes;         /* bytes of block_ (what the device-to-host copy moved)     */
+  void *block_;
+} gq_pileup_elements;
+#ifdef __cplusplus
+static_assert(sizeof(gq_pileup_elements_params) == 8, "gq_pileup_elements_params layout");
+static_assert(sizeof(gq_pileup_elements) == 256, "gq_pileup_elements layout");
+#endif
+gq_status gq_pileup_elements_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
+                                  const gq_pileup_elements_params *params, gq_pileup_elements **out);
+void gq_free_pileup_elements(gq_pileup_elements *res);
+
 /* vaf-histogram: VAFHistogram.variantLociFromReads + generateVAFHistogram
  * (commands/VAFHistogram.scala:208-229, 188-196): at every visited locus whose pileup holds a
  * non-Match element (VariantLocus.apply, :31-37), VAF = (depth - referenceDepth).toFloat /
