@@ -1968,7 +1968,9 @@ gq_status gq_bam_dev_reads(gq_bam_dev *b, const uint8_t *class_sample, int32_t n
   HIP_TRY(alloc(sizeof(int64_t) * n0, &p)); F.md_off = (int64_t *)p;
   HIP_TRY(alloc(sizeof(int32_t) * n0, &p)); F.n_md = (int32_t *)p;
   HIP_TRY(alloc(sizeof(uint16_t) * n0, &p)); F.n_mismatch = (uint16_t *)p;
-  HIP_TRY(alloc((size_t)b->seq_bytes + kSeqPad, &p)); F.seq = (uint8_t *)p;
+  // (a zeroed head in front of the sequence pool as well: DevReads::seq_head)
+  HIP_TRY(alloc(kSeqHead + (size_t)b->seq_bytes + kSeqPad, &p)); F.seq = (uint8_t *)p + kSeqHead;
+  HIP_TRY(hipMemsetAsync(p, 0, kSeqHead, c->stream));
   HIP_TRY(hipMemsetAsync(F.seq + b->seq_bytes, 0, kSeqPad, c->stream));
   HIP_TRY(alloc((size_t)b->seq_bytes + kSeqPad, &p)); F.qual = (uint8_t *)p;
   HIP_TRY(hipMemsetAsync(F.qual + b->seq_bytes, 0, kSeqPad, c->stream));
@@ -2034,6 +2036,7 @@ gq_status gq_bam_dev_reads(gq_bam_dev *b, const uint8_t *class_sample, int32_t n
   R.md_ev = F.md_ev;
   R.seq_bytes = b->seq_bytes;
   R.seq_cap = b->seq_bytes + kSeqPad;
+  R.seq_head = (int32_t)kSeqHead;
   R.cigar_len = b->cigar_len;
   R.md_len = b->md_events;
   if (sample_hash) {

@@ -291,8 +291,12 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
             const int64_t o = __shfl_xor(so_min, d, 64);
             so_min = o < so_min ? o : so_min;
           }
-          defer = !DEEP && so_min < 8;  // the pool's head: the DEEP instantiation (shifted loads)
-          tbase = so_min >= 8 ? so_min - 8 : 0;  // (uniform: the buffer descriptor in scalar registers)
+          // the pool's head: a pool with a readable head (DevReads::seq_head, zeroed; its bytes lie
+          // outside every run and are masked out of the counts and of badb) takes a base below its
+          // first byte, down to -8; one without goes to the DEEP instantiation (shifted loads)
+          const bool headed = R.seq_head >= 8 && so_min >= 0;  // (so_min < 0: an invalid set, as before)
+          defer = !DEEP && so_min < 8 && !headed;
+          tbase = so_min >= 8 || headed ? so_min - 8 : 0;  // (uniform: the buffer descriptor in scalar registers)
           tbase = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)tbase >> 32)) << 32) |
                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)tbase));
           const int64_t span = R.seq_cap - tbase;
@@ -420,8 +424,9 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
           const int32_t s16 = (int32_t)(int16_t)(d.x & 0xFFFFu), e16 = (int32_t)(int16_t)(d.x >> 16);
           const int32_t a = min(max(s16 - colr, 0), 8), b = min(max(e16 - colr, 0), 8);
           const bool live = mine && b > a && !(dbg & 1);
-          // (vi >= -7 for a live pair, byte a being the run's; < 0 only at the pool's head, whose
-          // tiles the DEEP instantiation takes: its load clamped to the base and shifted back)
+          // (vi >= -7 for a live pair, byte a being the run's; < 0 only at the head of a pool with
+          // no readable head, whose tiles the DEEP instantiation takes: its load clamped to the
+          // base and shifted back)
           const int32_t vi = (int32_t)d.y + colr;
           const uint32_t vo = live ? (uint32_t)(DEEP ? max(vi, 0) : vi) : 0x80000000u;
           if (GQ_DIR_MASKED) {  // dead lanes off the load (exec-masked) instead of out of range

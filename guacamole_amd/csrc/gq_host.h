@@ -35,6 +35,8 @@ constexpr int kGermT = 512;  // loci per germline tile
 constexpr int kCountT = 512;  // loci per counts tile
 constexpr size_t kSeqPad = 2048;  // zeroed tail of the uploaded sequence pool  // LDS staging of a read batch's sequence bytes
 
+constexpr size_t kSeqHead = 16;  // zeroed head in front of it (DevReads::seq_head; seq stays 16-byte aligned)
+
 constexpr int kSpread = 64;
 constexpr int kPartsCols = 2048;  // [0, 2048): one output partition per germline workgroup
 constexpr int kPartsWalk = 1024;  // then one per walker / complex-kernel wave (modulo)

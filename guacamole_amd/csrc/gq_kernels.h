@@ -42,6 +42,10 @@ struct DevReads {
   const uint32_t *cigar, *md_ev;
   int64_t seq_bytes;
   int64_t seq_cap;  // readable bytes of the device seq allocation (>= seq_bytes; padded on upload)
+  // readable, zeroed bytes in front of seq[0] (kSeqHead where the project allocates the pool: the
+  // host upload and the device BAM loader; 0 for a wrapped, caller-owned pool).  With 8 or more,
+  // germline_direct's 8-byte column loads of the pool's head tile start inside the allocation.
+  int32_t seq_head;
   int64_t cigar_len, md_len;  // pool sizes (upload-time bounds checks)
   // derived at upload (read_shape):
   const int16_t *lead;   // leading soft clip of a [S|H]*(M|=|X)[S|H]* CIGAR, -1 otherwise

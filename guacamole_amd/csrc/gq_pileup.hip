@@ -164,9 +164,12 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // Tile planning
 // ------------------------------------------------------------------------------------------
-// The block index of the reads (DevReads::blk_rb / blk_rs): one thread per 512-locus block.
-__global__ void block_index(DevReads R, int64_t n_blocks, int64_t *__restrict__ blk_rb, int64_t *__restrict__ blk_rs) {
-  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// The block index of the reads (DevReads::blk_rb / blk_rs): one thread per 512-locus block
+// (wg: the workgroup's place among those of the index).  Reads start, pmax_end, qoff and
+// contig_read_begin; writes blk_rb and blk_rs.
+__device__ __forceinline__ void block_index_body(const DevReads &R, int64_t wg, int64_t n_blocks,
+                                                 int64_t *__restrict__ blk_rb, int64_t *__restrict__ blk_rs) {
+  const int64_t g = wg * blockDim.x + threadIdx.x;
   if (g >= n_blocks) return;
   int lo = 0, hi = R.n_contigs - 1;  // the contig: last c with qoff[c] / 4 <= g
   while (lo < hi) {
@@ -191,6 +194,11 @@ __global__ void block_index(DevReads R, int64_t n_blocks, int64_t *__restrict__ 
     else a0 = m + 1;
   }
   blk_rs[g] = a0;
+}
+// (the first derivation of a set: its block count comes from pmax_end values read back after
+// read_prep; a re-derivation runs both in one launch, derive_reads)
+__global__ void block_index(DevReads R, int64_t n_blocks, int64_t *__restrict__ blk_rb, int64_t *__restrict__ blk_rs) {
+  block_index_body(R, (int64_t)blockIdx.x, n_blocks, blk_rb, blk_rs);
 }
 
 __global__ void plan_tiles(const int32_t *__restrict__ r_contig, const int64_t *__restrict__ r_start,
@@ -901,12 +909,27 @@ __global__ void ev_bases(DevReads R, uint8_t *__restrict__ ev_rb) {
 // The upload-time checks (validate_one) and the read shapes (shape_one) in one pass over the
 // reads: a read whose own offsets lie outside their pools (bit 2) gets no shape (the upload fails
 // on the flag anyway).
-__global__ void read_prep(DevReads R, int *__restrict__ bad, int16_t *__restrict__ lead) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// Reads the SoA arrays and the cigar pool; writes lead and the flag.
+__device__ __forceinline__ void read_prep_body(const DevReads &R, int64_t wg, int *__restrict__ bad,
+                                               int16_t *__restrict__ lead) {
+  const int64_t r = wg * blockDim.x + threadIdx.x;
   if (r >= R.n_reads) return;
   const int b = validate_one(R, r);
   if (b) atomicOr(bad, b);
   shape_one(R, r, lead, (b & 2) != 0);  // (its loads go out beside validate_one's)
+}
+__global__ void read_prep(DevReads R, int *__restrict__ bad, int16_t *__restrict__ lead) {
+  read_prep_body(R, (int64_t)blockIdx.x, bad, lead);
+}
+// A re-derivation's two halves in one grid: the first n_blk_wg workgroups build the block index,
+// the rest (rebased) run read_prep.  The halves are independent: the index reads start, pmax_end,
+// qoff and contig_read_begin, none of which read_prep writes (it writes lead and the flag only),
+// and read_prep reads neither blk_rb nor blk_rs.  The index's workgroups come first so their
+// dependent binary searches (latency only) run under the streaming half instead of behind it.
+__global__ void derive_reads(DevReads R, unsigned n_blk_wg, int64_t n_blocks, int64_t *__restrict__ blk_rb,
+                             int64_t *__restrict__ blk_rs, int *__restrict__ bad, int16_t *__restrict__ lead) {
+  if (blockIdx.x < n_blk_wg) block_index_body(R, (int64_t)blockIdx.x, n_blocks, blk_rb, blk_rs);
+  else read_prep_body(R, (int64_t)(blockIdx.x - n_blk_wg), bad, lead);  // (the branch is uniform per workgroup)
 }
 
 __device__ __forceinline__ uint64_t pack_inline(uint8_t r0, const uint8_t *alt, int alt_len) {
@@ -2054,15 +2077,34 @@ static gq_status derive_shape_impl(gq_ctx *c, gq_dev_reads *d, int64_t md_len, b
   const int nc = d->d.n_contigs;
   const bool reuse = lazy && d->shape_kept;  // (a re-derivation: nothing below waits for the device)
   std::vector<int32_t> last((size_t)nc, 0);  // each contig's largest read end (pmax_end of its last read)
-  if (d->d.n_reads > 0) {
-    void *flag = nullptr;
+  // the block index of the reads (plan_tiles' windows of aligned tiles).  A re-derivation knows
+  // its size (n_slices_kept) and its slice offsets (qoff_dev) already: the index is built in
+  // read_prep's launch (derive_reads), not behind it
+  int64_t n_blk = 0, *brb = nullptr, *brs = nullptr;
+  auto index_buffers = [&]() -> hipError_t {
+    n_blk = d->n_slices_kept / 4;
+    void *bi = nullptr;
+    const hipError_t e = d->dp.get(&bi, sizeof(int64_t) * 2 * (size_t)std::max<int64_t>(n_blk, 1));
+    brb = (int64_t *)bi;
+    brs = brb + std::max<int64_t>(n_blk, 1);
+    return e;
+  };
+  void *flag = nullptr;
+  const unsigned nb = (unsigned)((d->d.n_reads + kBlock - 1) / kBlock);  // read_prep's workgroups
+  if (nb) {
     HIP_TRY(d->dp.get(&flag, sizeof(int)));
     HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-    const unsigned nb = (unsigned)((d->d.n_reads + kBlock - 1) / kBlock);
-    // validation and the read shapes in one pass (a read out of its pools gets no shape)
-    hipLaunchKernelGGL(read_prep, dim3(nb), dim3(kBlock), 0, c->stream, d->d, (int *)flag, (int16_t *)p);
-    HIP_TRY(hipGetLastError());
-    if (reuse) {
+  }
+  if (reuse) {
+    d->d.qoff = d->qoff_dev;
+    HIP_TRY(index_buffers());
+    const unsigned n_blk_wg = (unsigned)((n_blk + kBlock - 1) / kBlock);
+    if (n_blk_wg + nb) {  // (either half may be empty: no reads, or no read reaching a block)
+      hipLaunchKernelGGL(derive_reads, dim3(n_blk_wg + nb), dim3(kBlock), 0, c->stream, d->d, n_blk_wg, n_blk, brb, brs,
+                         (int *)flag, (int16_t *)p);
+      HIP_TRY(hipGetLastError());
+    }
+    if (nb) {
       // the flag travels behind the kernel; whoever next waits for the stream checks it
       // (validation_settled: settle_stats, or the next call on the set)
       if (!d->vflag) HIP_TRY(hipHostMalloc((void **)&d->vflag, sizeof(int), hipHostMallocDefault));
@@ -2070,19 +2112,22 @@ static gq_status derive_shape_impl(gq_ctx *c, gq_dev_reads *d, int64_t md_len, b
       HIP_TRY(hipMemcpyAsync(d->vflag, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       d->vflag_pending = true;
       unordered = d->pool_ordered_kept ? 0 : 1;
-    } else {
-      int bad = 0;
-      HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      const auto &crb = d->contig_read_begin;
-      for (int k = 0; k < nc; ++k)
-        if (crb[(size_t)k + 1] > crb[(size_t)k])
-          HIP_TRY(hipMemcpyAsync(&last[(size_t)k], d->d.pmax_end + (crb[(size_t)k + 1] - 1), sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const gq_status vs = validation_status(bad);
-      if (vs) return vs;
-      unordered = (bad & 4) ? 1 : 0;
     }
+  } else if (nb) {
+    // validation and the read shapes in one pass (a read out of its pools gets no shape)
+    hipLaunchKernelGGL(read_prep, dim3(nb), dim3(kBlock), 0, c->stream, d->d, (int *)flag, (int16_t *)p);
+    HIP_TRY(hipGetLastError());
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    const auto &crb = d->contig_read_begin;
+    for (int k = 0; k < nc; ++k)
+      if (crb[(size_t)k + 1] > crb[(size_t)k])
+        HIP_TRY(hipMemcpyAsync(&last[(size_t)k], d->d.pmax_end + (crb[(size_t)k + 1] - 1), sizeof(int32_t),
+                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const gq_status vs = validation_status(bad);
+    if (vs) return vs;
+    unordered = (bad & 4) ? 1 : 0;
   }
   {  // the projections' slices (whole 512-locus blocks up to each contig's largest read end) and
      // the block index of the reads (plan_tiles' windows of aligned tiles); the projection
@@ -2109,14 +2154,13 @@ static gq_status derive_shape_impl(gq_ctx *c, gq_dev_reads *d, int64_t md_len, b
     }
     d->d.qoff = d->qoff_dev;
     d->n_slices = d->n_slices_kept;
-    const int64_t n_blk = d->n_slices_kept / 4;
-    void *bi = nullptr;
-    HIP_TRY(d->dp.get(&bi, sizeof(int64_t) * 2 * (size_t)std::max<int64_t>(n_blk, 1)));
-    int64_t *brb = (int64_t *)bi, *brs = brb + std::max<int64_t>(n_blk, 1);
-    if (n_blk > 0) {
-      hipLaunchKernelGGL(block_index, dim3((unsigned)((n_blk + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, d->d,
-                         n_blk, brb, brs);
-      HIP_TRY(hipGetLastError());
+    if (!reuse) {  // (its block count is known only now: the index in a launch of its own)
+      HIP_TRY(index_buffers());
+      if (n_blk > 0) {
+        hipLaunchKernelGGL(block_index, dim3((unsigned)((n_blk + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, d->d,
+                           n_blk, brb, brs);
+        HIP_TRY(hipGetLastError());
+      }
     }
     d->d.blk_rb = brb;
     d->d.blk_rs = brs;
@@ -2153,25 +2197,33 @@ gq_status gq_reads_upload(gq_ctx *c, const gq_reads *h, gq_dev_reads **out) {
     }
   }
   // src_range(out, o, k): bytes [o, o + k) of the array in its device layout
-  auto up_from = [&](size_t bytes, void **dst, size_t pad, const auto &src_range) -> hipError_t {
+  // head: zeroed bytes in front of the array (the returned pointer stands behind them)
+  auto alloc_head = [&](size_t bytes, void **dst, size_t head) -> hipError_t {
     *dst = nullptr;
-    hipError_t e = hipMalloc(dst, std::max(bytes + pad, (size_t)16));
+    hipError_t e = hipMalloc(dst, std::max(head + bytes, (size_t)16));
     if (e != hipSuccess) return e;
     d->owned.push_back(*dst);
+    if (head) {
+      e = hipMemsetAsync(*dst, 0, head, c->stream);
+      *dst = (char *)*dst + head;
+    }
+    return e;
+  };
+  auto up_from = [&](size_t bytes, void **dst, size_t pad, size_t head, const auto &src_range) -> hipError_t {
+    hipError_t e = alloc_head(bytes + pad, dst, head);
+    if (e != hipSuccess) return e;
     if (bytes) e = stager.copy_from(*dst, bytes, src_range);
     if (e == hipSuccess && pad) e = hipMemsetAsync((char *)*dst + bytes, 0, pad, c->stream);
     return e;
   };
-  auto up = [&](const void *src, size_t bytes, void **dst, size_t pad) -> hipError_t {
+  auto up = [&](const void *src, size_t bytes, void **dst, size_t pad, size_t head) -> hipError_t {
     if (bytes >= (size_t(1) << 20) || (!src && bytes))  // (a null source reads as zeros)
-      return up_from(bytes, dst, pad, [src](uint8_t *out, size_t o, size_t k) {
+      return up_from(bytes, dst, pad, head, [src](uint8_t *out, size_t o, size_t k) {
         if (src) memcpy(out, (const uint8_t *)src + o, k);
         else memset(out, 0, k);
       });
-    *dst = nullptr;
-    hipError_t e = hipMalloc(dst, std::max(bytes + pad, (size_t)16));
+    hipError_t e = alloc_head(bytes + pad, dst, head);
     if (e != hipSuccess) return e;
-    d->owned.push_back(*dst);
     if (bytes) e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && pad) e = hipMemsetAsync((char *)*dst + bytes, 0, pad, c->stream);
     return e;
@@ -2186,7 +2238,9 @@ gq_status gq_reads_upload(gq_ctx *c, const gq_reads *h, gq_dev_reads **out) {
     }                                                                           \
     d->d.field = (const T *)p;                                                  \
   } while (0)
-#define UP(field, count, T) UP_CHECK(field, T, up(h->field, (size_t)(count) * sizeof(T), &p, pad_##field))
+#define UP_HEAD(field, count, T, head) \
+  UP_CHECK(field, T, up(h->field, (size_t)(count) * sizeof(T), &p, pad_##field, head))
+#define UP(field, count, T) UP_HEAD(field, count, T, 0)
   // the sequence pool gets a zeroed tail so 1 KiB LDS-DMA pieces and 16-byte chunk loads
   // past the last read stay inside the allocation (DevReads::seq_cap)
   enum : size_t { pad_contig_read_begin = 0, pad_start = 0, pad_end = 0, pad_pmax_end = 0, pad_mapq = 0, pad_flags = 0,
@@ -2245,20 +2299,24 @@ gq_status gq_reads_upload(gq_ctx *c, const gq_reads *h, gq_dev_reads **out) {
   UP(md_off, n, int64_t);
   UP(n_md, n, int32_t);
   UP(n_mismatch, n, uint16_t);
+  // (the sequence pool alone gets the head: germline_direct reads it; somatic_direct clamps its
+  // tile base at the pool's first byte and reads seq and qual from one base, so qual has none)
   if (ordered) {
-    UP(seq, h->seq_bytes, uint8_t);
+    UP_HEAD(seq, h->seq_bytes, uint8_t, kSeqHead);
     UP(qual, h->seq_bytes, uint8_t);
   } else {
-    UP_CHECK(seq, uint8_t, up_from((size_t)h->seq_bytes, &p, pad_seq, gather(h0->seq)));
-    UP_CHECK(qual, uint8_t, up_from((size_t)h->seq_bytes, &p, pad_qual, gather(h0->qual)));
+    UP_CHECK(seq, uint8_t, up_from((size_t)h->seq_bytes, &p, pad_seq, kSeqHead, gather(h0->seq)));
+    UP_CHECK(qual, uint8_t, up_from((size_t)h->seq_bytes, &p, pad_qual, 0, gather(h0->qual)));
   }
   UP(cigar, h->cigar_len, uint32_t);
   UP(md_ev, h->md_len, uint32_t);
 #undef UP
+#undef UP_HEAD
 #undef UP_CHECK
   d->d.n_reads = n;
   d->d.seq_bytes = h->seq_bytes;
   d->d.seq_cap = h->seq_bytes + kSeqPad;
+  d->d.seq_head = (int32_t)kSeqHead;
   d->d.cigar_len = h->cigar_len;
   d->d.md_len = h->md_len;
   d->d.n_contigs = h->n_contigs;
@@ -2301,6 +2359,7 @@ gq_status gq_reads_wrap_device(gq_ctx *c, const gq_reads *h, gq_dev_reads **out)
   d->d.n_reads = h->n_reads;
   d->d.seq_bytes = h->seq_bytes;
   d->d.seq_cap = h->seq_bytes;  // caller-owned buffer: no readable tail assumed
+  d->d.seq_head = 0;            // (nor a readable head)
   d->d.cigar_len = h->cigar_len;
   d->d.md_len = h->md_len;
   d->d.n_contigs = h->n_contigs;
