@@ -975,6 +975,111 @@ def pileup_elements_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def somatic_likelihoods_reads(ctx: native.Context, tumor: ReadSet, normal: ReadSet, loci, **params) -> List[dict]:
+    """What findPotentialVariantAtLocus (SomaticStandardCaller.scala:162-245) computes before it keeps
+    one allele and applies --odds, at every locus pileupFlatMapTwoRDDs(tumor, normal, partitions,
+    skipEmpty=true) visits where the caller's gate passes (gq_somatic_likelihoods_call).  params:
+    min_mapq (1), filter_multi_allelic (False), max_read_depth (2**31 - 1).  Groups as
+    native.SomaticLikelihoods.groups with the contig by name, loci in call order."""
+    if tumor.contig_names != normal.contig_names:
+        raise ValueError("tumor and normal reads must share the contig list")
+    res = ctx.somatic_likelihoods(device_reads(ctx, tumor), device_reads(ctx, normal), loci, **params)
+    groups = []
+    for g in res.groups:
+        g = dict(g)
+        g["contig"] = tumor.contig_names[g["contig"]]
+        groups.append(g)
+    return groups
+
+
+SOMATIC_LIKELIHOODS_HEADER = ("contig,locus,tumorRefBase,normalRefBase,tumorDepth,normalDepth,sample,genotype,ref1,alt1,"
+                              "ref2,alt2,alleleDepth1,alleleDepth2,logLikelihood,best,hasVariant,normalVariantTotal,"
+                              "logOdds,flags")
+
+
+def write_somatic_likelihoods_csv(path: str, groups: List[dict]) -> None:
+    """The groups of somatic_likelihoods_reads as CSV (SOMATIC_LIKELIHOODS_HEADER), one line per
+    genotype: the tumor's genotypes then the normal's (`sample` says which, `genotype` is its index
+    among that sample's), the group's best, hasVariant, normalVariantTotal and logOdds repeated on
+    each line.  Doubles as repr() writes them (they read back to the same bits), NaN as "NaN", the
+    infinities as "Infinity" / "-Infinity".  Refuses an existing path."""
+    def num(x: float) -> str:
+        if x != x:
+            return "NaN"
+        if x in (float("inf"), float("-inf")):
+            return "Infinity" if x > 0 else "-Infinity"
+        return repr(x)
+    with open(path, "x") as fh:
+        fh.write(SOMATIC_LIKELIHOODS_HEADER + "\n")
+        for g in groups:
+            head = [g["contig"], str(g["locus"]), g["tumor_ref_base"], g["normal_ref_base"], str(g["tumor_depth"]),
+                    str(g["normal_depth"])]
+            tail = [str(g["best"]), "1" if g["has_variant"] else "0", num(g["normal_variant_total"]), num(g["log_odds"]),
+                    str(g["flags"])]
+            for side in ("tumor", "normal"):
+                al, ll = g[side + "_alleles"], g[side + "_log_likelihoods"]
+                k = 0
+                for i in range(len(al)):
+                    for j in range(i, len(al)):
+                        fh.write(",".join(head + [side, str(k), al[i][0], al[i][1], al[j][0], al[j][1], str(al[i][2]),
+                                                  str(al[j][2]), num(ll[k])] + tail) + "\n")
+                        k += 1
+
+
+def somatic_likelihoods_main(argv: Sequence[str]) -> int:
+    """somatic-likelihoods: both samples' genotype log-likelihoods, the most likely tumor genotype,
+    the normal's variant mass and the somatic log-odds at every locus that passes somatic-standard's
+    gate, as CSV.  Input filters as somatic-standard's (SomaticStandardCaller.scala:82-89)."""
+    import os
+    p = argparse.ArgumentParser(prog="somatic-likelihoods",
+                                description="tumor / normal genotype log-likelihoods and somatic log-odds at every "
+                                            "locus somatic-standard evaluates")
+    p.add_argument("--tumor-reads", required=True, help="Aligned reads: tumor")
+    p.add_argument("--normal-reads", required=True, help="Aligned reads: normal")
+    p.add_argument("--out", required=True, help="Output CSV path (must not exist)")
+    p.add_argument("--loci", default="", help="Loci to visit (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    p.add_argument("--min-mapq", type=int, default=1, help="Minimum read mapping quality for a read (Phred-scaled)")
+    p.add_argument("--filter-multi-allelic", action="store_true", help="Filter any pileups > 2 bases considered")
+    p.add_argument("--max-read-depth", type=int, default=2 ** 31 - 1, help="Skip loci with a deeper filtered pileup")
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("somatic-likelihoods")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    builder = _loci_builder(args)
+    f = InputFilters.make(overlaps_loci=builder, non_duplicate=True, passed_vendor_quality_checks=True,
+                          has_md_tag=True)
+    ctx = None
+    sets = [None, None]
+    if device_ingest(args, args.tumor_reads, args.normal_reads):
+        maps = map_bams([args.tumor_reads, args.normal_reads])
+        ctx = native.Context(args.device)
+        ctx2 = native.Context(args.device)  # the normal's load: its own stream, alongside the tumor's
+        sets = load_pair_device(ctx, ctx2, [args.tumor_reads, args.normal_reads], f, maps["join"]())
+    tumor, normal = [s if s is not None else load_reads(path, f, recompute_md=args.recompute_md_tags)
+                     for s, path in zip(sets, (args.tumor_reads, args.normal_reads))]
+    if tumor.contig_lengths_map != normal.contig_lengths_map:
+        raise ValueError("Tumor and normal samples have different sequence dictionaries.")
+    loci = builder.result(normal.contig_lengths_map)
+    parts = partition(loci, args.parallelism, args.partition_accuracy, tumor, normal)
+    flat = flatten_partitions(parts, tumor.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    groups = somatic_likelihoods_reads(ctx, tumor, normal, flat, min_mapq=args.min_mapq,
+                                       filter_multi_allelic=args.filter_multi_allelic,
+                                       max_read_depth=args.max_read_depth)
+    write_somatic_likelihoods_csv(args.out, groups)
+    print("Wrote %d genotype likelihoods of %d loci." %
+          (sum(len(g["tumor_log_likelihoods"]) + len(g["normal_log_likelihoods"]) for g in groups), len(groups)),
+          file=sys.stderr)
+    return 0
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -987,9 +1092,9 @@ def warn_default_parallelism(args, world: int) -> None:
 
 
 def single_process_only(command: str) -> None:
-    """germline-standard, variant-support, vaf-histogram, allele-evidence, genotype-likelihoods and
-    pileup-elements run as one process on --device: under torch.distributed.run every rank would repeat the whole
-    job and write the same output, so a multi-rank launch is refused."""
+    """germline-standard, variant-support, vaf-histogram, allele-evidence, genotype-likelihoods,
+    pileup-elements and somatic-likelihoods run as one process on --device: under torch.distributed.run
+    every rank would repeat the whole job and write the same output, so a multi-rank launch is refused."""
     import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("%s runs as a single process (WORLD_SIZE=%s): launch it without torch.distributed.run "
@@ -1013,7 +1118,7 @@ def _finish_rank(rc: int) -> int:
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
-            "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main}
+            "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -1256,6 +1256,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
 #include "gq_allele_evidence.h"
 #include "gq_genotype_likelihoods.h"
 #include "gq_pileup_elements.h"
+#include "gq_somatic_likelihoods.h"
 
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
   const int key = 2 * min_mapq + (incl_align ? 1 : 0);  // the projection's filter and probability model
@@ -3078,6 +3079,454 @@ gq_status gq_pileup_elements_call(gq_ctx *c, const gq_dev_reads *rd, const gq_lo
 }
 
 void gq_free_pileup_elements(gq_pileup_elements *r) {
+  if (!r) return;
+  free(r->block_);  // one block holds every array
+  free(r);
+}
+
+namespace {
+SlLayout sl_layout(int64_t n_groups, const int64_t (&n_alleles)[2], const int64_t (&n_geno)[2], int64_t dev_pool_used) {
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t N = (size_t)n_groups;
+  SlLayout L;
+  L.contig = 64;
+  L.pos = al(L.contig + 4 * N);
+  L.flags = al(L.pos + 8 * N);
+  L.t_ref_base = al(L.flags + N);
+  L.n_ref_base = al(L.t_ref_base + N);
+  L.t_depth = al(L.n_ref_base + N);
+  L.n_depth = al(L.t_depth + 4 * N);
+  L.t_n_alleles = al(L.n_depth + 4 * N);
+  L.n_n_alleles = al(L.t_n_alleles + 4 * N);
+  L.t_allele_first = al(L.n_n_alleles + 4 * N);
+  L.n_allele_first = al(L.t_allele_first + 8 * N);
+  L.t_geno_first = al(L.n_allele_first + 8 * N);
+  L.n_geno_first = al(L.t_geno_first + 8 * N);
+  L.best = al(L.n_geno_first + 8 * N);
+  L.has_variant = al(L.best + 4 * N);
+  L.var_total = al(L.has_variant + N);
+  L.log_odds = al(L.var_total + 8 * N);
+  size_t at = al(L.log_odds + 8 * N);
+  for (int s = 0; s < 2; ++s) {
+    const size_t A = (size_t)n_alleles[s];
+    L.a_ref_off[s] = at;
+    L.a_ref_len[s] = al(L.a_ref_off[s] + 8 * A);
+    L.a_alt_off[s] = al(L.a_ref_len[s] + 4 * A);
+    L.a_alt_len[s] = al(L.a_alt_off[s] + 8 * A);
+    L.a_depth[s] = al(L.a_alt_len[s] + 4 * A);
+    at = al(L.a_depth[s] + 4 * A);
+    L.n_alleles[s] = n_alleles[s];
+    L.n_geno[s] = n_geno[s];
+  }
+  L.ll[0] = at;
+  L.ll[1] = al(L.ll[0] + 8 * (size_t)n_geno[0]);
+  L.pool = al(L.ll[1] + 8 * (size_t)n_geno[1]);
+  // inline alleles hold <= 8 bytes; longer ones live in the device pool (each used once)
+  L.pool_cap = 8 * (n_alleles[0] + n_alleles[1]) + dev_pool_used + 1;
+  L.bytes = al(L.pool + (size_t)L.pool_cap);
+  return L;
+}
+
+// The call into `res` (zeroed; the caller frees it, block included, when this fails).
+gq_status somatic_likelihoods_run(gq_ctx *c, const gq_dev_reads *t, const gq_dev_reads *n, const gq_loci *loci,
+                                  const gq_somatic_likelihood_params *p, gq_somatic_likelihoods *res) {
+  const int dbg = getenv("GQ_DBG") ? atoi(getenv("GQ_DBG")) : 0;  // diagnostics only (read per call)
+  const auto h0 = std::chrono::steady_clock::now();
+  c->timings = gq_timings{};
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  // the locus list is somatic-standard's candidate pass with the hom-ref bound off
+  static const bool som_proj = getenv("GQ_SOM") && strcmp(getenv("GQ_SOM"), "proj") == 0;
+  const bool direct = !som_proj && t->d.seq_cap >= 8;
+  Plan pt, pn;
+  gq_status st = direct ? GQ_OK : ensure_projection(c, t);
+  if (st) return st;
+  st = plan(c, t, loci, SomProjCfg::kT, pt, c->tiles, 0, 0, 0, true);
+  if (st) return st;
+  st = plan(c, n, loci, SomProjCfg::kT, pn, c->tiles2, 0, 0, 0, true);
+  if (st) return st;
+  if (pt.n_tiles == 0) return GQ_OK;
+  {  // the phred -> success probability table, as the callers fill it
+    double succ[256];
+    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  SomWin sw{};
+  st = build_somwin(c, pt, t, n, sw);
+  if (st) return st;
+  if (direct) {
+    if (c->mtab_key != 1) {
+      HIP_TRY(c->mtab.ensure(256 * 256));
+      hipLaunchKernelGGL(margin_table, dim3(256), dim3(256), 0, c->stream, 1, (uint8_t *)c->mtab.p);
+      HIP_TRY(hipGetLastError());
+      c->mtab_key = 1;
+    }
+  } else {
+    st = ensure_margin_projection(c, t, (int)p->min_mapq);
+    if (st) return st;
+  }
+  const RefView rv{nullptr, nullptr};
+  OutGeom og{};
+  {
+    if (c->n_cu <= 0 &&
+        hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+      c->n_cu = 256;
+    int &wg_cu = direct ? c->somd_wg_per_cu : c->som_wg_per_cu;
+    if (wg_cu <= 0) {
+      int nb = 0;
+      const hipError_t e =
+          direct ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, somatic_direct<false>, SomDirCfg::kThreads, 0)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, somatic_proj<false>, SomProjCfg::kThreads, 0);
+      if (e != hipSuccess || nb <= 0) nb = direct ? 2 : 4;
+      wg_cu = nb;
+    }
+    og.ncols = (int)std::max<int64_t>(1, std::min<int64_t>({(pt.n_tiles + SomProjCfg::kWaves - 1) / SomProjCfg::kWaves,
+                                                           (int64_t)wg_cu * c->n_cu, (int64_t)kPartsCols}));
+    const unsigned long long wg_loci = (unsigned long long)((pt.n_tiles + og.ncols - 1) / og.ncols) * SomProjCfg::kT;
+    // without the bound every tumor-non-match locus is listed: a larger share of the loci than the
+    // caller's candidates (grown on overflow, part_scan's part_max)
+    og.capA[1] = wg_loci / 2 + 256;
+    og.capB[1] = (unsigned long long)pt.n_loci / 65536 + 1024;
+  }
+  const gq_somatic_params sp{0, p->min_mapq, p->filter_multi_allelic, p->max_read_depth};  // (the rest unread)
+  // a buffer that overflowed is grown to what the pass needed and the pass repeated; each buffer
+  // has its own budget of two growths (the heap-order pass can add to what the first one needed)
+  enum { B_LIST, B_AMB, B_DEEP, B_ALLELE, B_LL, B_POOL, B_N };
+  int grown[B_N] = {};
+  bool spent = false;
+  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
+    if (need <= cap) return false;
+    if (++grown[which] > 2) spent = true;
+    cap = need + slack;
+    return true;
+  };
+  unsigned long long allele_cap = 0, ll_cap = 0, pool_cap = 1 << 16, amb_cap = 4096, deep_cap = 4096;
+  Counters hc{};
+  unsigned long long n_cand = 0;
+  float deep_ms = 0;
+  for (;;) {
+    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
+    HIP_TRY(c->cplx.ensure(og.total(1) * sizeof(ComplexItem)));
+    HIP_TRY(c->pool.ensure(pool_cap));
+    HIP_TRY(c->slow.ensure((size_t)pt.n_tiles * sizeof(int32_t)));
+    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    Counters *ctr = (Counters *)c->counters.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (direct)
+      hipLaunchKernelGGL(somatic_direct<false>, dim3((unsigned)og.ncols), dim3(SomDirCfg::kThreads), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const Tile *)c->tiles2.p, pt.n_tiles, t->d, n->d.start, n->d.end,
+                         (const uint8_t *)c->mtab.p, (int)p->min_mapq, (ComplexItem *)c->cplx.p, og, ctr,
+                         (int32_t *)c->slow.p, rv, 1, 0);
+    else
+      hipLaunchKernelGGL(somatic_proj<false>, dim3((unsigned)og.ncols), dim3(SomProjCfg::kThreads), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const Tile *)c->tiles2.p, pt.n_tiles, t->d,
+                         (const uint8_t *)t->mproj, (const uint8_t *)t->mnb, n->d.start, n->d.end,
+                         (ComplexItem *)c->cplx.p, og, ctr, (int32_t *)c->slow.p, rv, 1);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((somatic_tile<SomProjCfg::kT>), dim3((unsigned)std::min<int64_t>(pt.n_tiles, 2048)), dim3(kBlock), 0,
+                       c->stream, (const Tile *)c->tiles.p, (const Tile *)c->tiles2.p, t->d, n->d,
+                       (ComplexItem *)c->cplx.p, og, (const int32_t *)c->slow.p, (int)p->min_mapq, ctr, rv, 1);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(part_scan_som, dim3(1), dim3(1024), 0, c->stream, ctr, og);
+    HIP_TRY(hipGetLastError());
+    {  // list overflow: grow and list again before the per-locus kernel runs
+      unsigned long long pm = 0;
+      HIP_TRY(hipMemcpyAsync(&pm, &ctr->part_max[1], sizeof(pm), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(&n_cand, &ctr->part_off[1][kParts], sizeof(n_cand), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (pm) {
+        if (++grown[B_LIST] > 2) return set_err(GQ_E_CAPACITY, "somatic-likelihoods: locus list capacity retries exhausted");
+        og.capA[1] += pm + 64;
+        og.capB[1] += pm + 64;
+        continue;
+      }
+    }
+    HIP_TRY(c->cands.ensure(sizeof(CandRec) * (size_t)std::max<unsigned long long>(n_cand, 1)));
+    hipLaunchKernelGGL(cand_prep, dim3((unsigned)((kParts + kSomWaves - 1) / kSomWaves)), dim3(kBlock), 0, c->stream,
+                       (const Tile *)c->tiles.p, (const Tile *)c->tiles2.p, (const ComplexItem *)c->cplx.p, og,
+                       (const Counters *)ctr, sw, t->d, n->d, (CandRec *)c->cands.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if (n_cand == 0) {
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      break;
+    }
+    // a listed locus gives at most one group; alleles and genotypes per group are guessed (a
+    // variant locus mostly holds 2 or 3 alleles per sample) and grown on overflow
+    const unsigned long long group_cap = n_cand;
+    allele_cap = std::max(allele_cap, 6 * group_cap + 4096);
+    ll_cap = std::max(ll_cap, 12 * group_cap + 4096);
+    HIP_TRY(c->srecs.ensure(group_cap * sizeof(SlGroup)));
+    HIP_TRY(c->recs.ensure(allele_cap * sizeof(GlAllele)));
+    HIP_TRY(c->recs_sorted.ensure(ll_cap * sizeof(double)));
+    HIP_TRY(c->deep_list.ensure(2 * deep_cap * sizeof(int64_t)));  // the deep list, then the wide list
+    const SlOut so{(SlGroup *)c->srecs.p, group_cap, (GlAllele *)c->recs.p, allele_cap,
+                   (double *)c->recs_sorted.p, ll_cap, (uint8_t *)c->pool.p, pool_cap};
+    if (c->sl_wg_per_cu <= 0) {
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)somatic_likelihoods_k<false>, kBlock, 0) !=
+              hipSuccess ||
+          nb <= 0)
+        nb = 3;
+      c->sl_wg_per_cu = nb;
+    }
+    const int cblocks = (int)std::min<int64_t>(((int64_t)n_cand + kSomWaves - 1) / kSomWaves,
+                                               (int64_t)c->sl_wg_per_cu * c->n_cu);
+    hipLaunchKernelGGL(somatic_likelihoods_k<false>, dim3(cblocks), dim3(kBlock), 0, c->stream,
+                       (const CandRec *)c->cands.p, t->d, n->d, sp, so, ctr, sw, (AmbItem *)c->amb.p, amb_cap,
+                       (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, dbg,
+                       DeepIO{(int64_t *)c->deep_list.p, deep_cap, 0, nullptr, 0, 0, nullptr, 0});
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    deep_ms = 0;
+    // the deep kernel (per-wave scratch sized from the deepest listed pileup) over the deep list or
+    // the heap-order loci; the wide kernel over what the deep one's table could not hold
+    auto run_deep = [&](int64_t n_items, const AmbItem *ain, const uint8_t *aref) -> gq_status {
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, (unsigned long long)kFastCap);
+      const int64_t nw = std::min<int64_t>(n_items, 4096);
+      HIP_TRY(c->deep_scratch.ensure((size_t)nw * deep_wave_bytes(scap, kMaxG) + 256));
+      HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+      hipLaunchKernelGGL(somatic_likelihoods_k<true>, dim3((unsigned)((nw + kSomWaves - 1) / kSomWaves)), dim3(kBlock),
+                         0, c->stream, (const CandRec *)c->cands.p, t->d, n->d, sp, so, ctr, sw,
+                         (AmbItem *)(ain ? nullptr : c->amb.p), ain ? (unsigned long long)0 : amb_cap, ain, aref,
+                         ain ? n_items : (int64_t)0, dbg,
+                         DeepIO{(int64_t *)c->deep_list.p, 0, ain ? 0 : n_items, (uint8_t *)c->deep_scratch.p, scap,
+                                kMaxG, (int64_t *)c->deep_list.p + deep_cap, deep_cap});
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[3]);
+      deep_ms += ms;
+      return GQ_OK;
+    };
+    auto run_wide = [&](int64_t n_items, const AmbItem *ain, const uint8_t *aref, int64_t n_ain) -> gq_status {
+      const int scap = (int)std::max<unsigned long long>(hc.deep_max, (unsigned long long)kFastCap);
+      const int maxg = 64 * kWideNS * (64 * kWideNS + 1) / 2;
+      const int64_t nw = std::min<int64_t>(n_items, 16);  // (12.6 MB of genotype scratch per wave)
+      HIP_TRY(c->deep_scratch.ensure((size_t)nw * deep_wave_bytes(scap, maxg, kWideNS) + 256));
+      HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+      hipLaunchKernelGGL((somatic_likelihoods_k<true, kWideNS>), dim3((unsigned)((nw + kSomWaves - 1) / kSomWaves)),
+                         dim3(kBlock), 0, c->stream, (const CandRec *)c->cands.p, t->d, n->d, sp, so, ctr, sw,
+                         (AmbItem *)(ain ? nullptr : c->amb.p), ain ? (unsigned long long)0 : amb_cap, ain, aref,
+                         ain ? n_ain : (int64_t)0, dbg,
+                         DeepIO{(int64_t *)c->deep_list.p + deep_cap, 0, n_items, (uint8_t *)c->deep_scratch.p, scap,
+                                maxg, nullptr, 0});
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[3]);
+      deep_ms += ms;
+      return GQ_OK;
+    };
+    bool retry = grow(B_DEEP, deep_cap, hc.n_deep, 1024);
+    if (!retry && hc.n_deep > 0 && !hc.err) {
+      st = run_deep((int64_t)hc.n_deep, nullptr, nullptr);
+      if (st) return st;
+    }
+    retry |= grow(B_DEEP, deep_cap, hc.n_wide, 1024);
+    if (!retry && hc.n_wide > 0 && !hc.err) {
+      st = run_wide((int64_t)hc.n_wide, nullptr, nullptr, 0);
+      if (st) return st;
+    }
+    retry |= grow(B_AMB, amb_cap, hc.n_amb, 1024);
+    if (!retry && hc.n_amb > 0 && !hc.err) {
+      // loci where a sample's reference base depends on heap order: replay both windows' queues,
+      // then the deep kernel over just those loci with the resolved bases
+      std::vector<AmbItem> amb((size_t)hc.n_amb);
+      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(c->amb_ref.ensure(2 * amb.size()));
+      st = heap_ref_bases(c, pt, c->tiles, {t, n}, amb, (uint8_t *)c->amb_ref.p);
+      if (st) return st;
+      // (the hand-over list of the replay starts empty: loci past the deep table go to the wide kernel)
+      HIP_TRY(hipMemsetAsync(&ctr->n_wide, 0, sizeof(ctr->n_wide), c->stream));
+      st = run_deep((int64_t)amb.size(), (const AmbItem *)c->amb.p, (const uint8_t *)c->amb_ref.p);
+      if (st) return st;
+      retry |= grow(B_DEEP, deep_cap, hc.n_wide, 1024);
+      if (!retry && hc.n_wide > 0 && !hc.err) {
+        st = run_wide((int64_t)hc.n_wide, (const AmbItem *)c->amb.p, (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
+        if (st) return st;
+      }
+    }
+    retry |= grow(B_ALLELE, allele_cap, hc.n_out, 4096);
+    retry |= grow(B_LL, ll_cap, hc.out_pool, 4096);
+    retry |= grow(B_POOL, pool_cap, hc.pool_used, 4096);
+    if (!retry || hc.err) break;
+    if (spent) return set_err(GQ_E_CAPACITY, "somatic-likelihoods: output capacity retries exhausted");
+  }
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  st = check_device_error(c, hc);
+  if (st) return st;
+  // ---- on the device: groups by locus ordinal, counts scanned to offsets, every column placed; one copy
+  const int64_t ng = n_cand > 0 ? (int64_t)hc.n_rec : 0;
+  int64_t n_all[2] = {0, 0}, n_geno[2] = {0, 0};
+  SlLayout lay = sl_layout(0, n_all, n_geno, 0);
+  if (ng > 0) {
+    const size_t nn = (size_t)ng;
+    HIP_TRY(c->keys.ensure(nn * 8));
+    HIP_TRY(c->keys_sorted.ensure(nn * 8));
+    HIP_TRY(c->idx.ensure(nn * 4));
+    HIP_TRY(c->idx_sorted.ensure(nn * 4));
+    HIP_TRY(c->cands.ensure(10 * nn * sizeof(int64_t)));
+    const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
+    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
+    int64_t *sc = (int64_t *)c->cands.p;  // (the listed loci's records: every per-locus kernel is done)
+    const Sl5 cnt{sc, sc + nn, sc + 2 * nn, sc + 3 * nn, sc + 4 * nn},
+        off{sc + 5 * nn, sc + 6 * nn, sc + 7 * nn, sc + 8 * nn, sc + 9 * nn};
+    hipLaunchKernelGGL(sl_keys, dim3(nb), dim3(kBlock), 0, c->stream, (const SlGroup *)c->srecs.p, ng, keys, slot);
+    HIP_TRY(hipGetLastError());
+    const uint64_t key_bound = (uint64_t)std::max<int64_t>(pt.n_loci, 1);
+    const int end_bit = 64 - __builtin_clzll(key_bound);
+    size_t tmp = 0, tmp2 = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.ta, off.ta, (int)ng, c->stream));
+    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
+                                               c->stream));
+    hipLaunchKernelGGL(sl_counts, dim3(nb), dim3(kBlock), 0, c->stream, (const SlGroup *)c->srecs.p,
+                       (const uint32_t *)order, ng, cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.ta, off.ta, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.na, off.na, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.tg, off.tg, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.ng, off.ng, (int)ng, c->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.p, off.p, (int)ng, c->stream));
+    // the samples' totals (the last group's offset + count) size the columns
+    int64_t last[4][2];
+    int64_t *const cols[4][2] = {{off.ta, cnt.ta}, {off.na, cnt.na}, {off.tg, cnt.tg}, {off.ng, cnt.ng}};
+    for (int q = 0; q < 4; ++q)
+      for (int h = 0; h < 2; ++h)
+        HIP_TRY(hipMemcpyAsync(&last[q][h], cols[q][h] + (nn - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    n_all[0] = last[0][0] + last[0][1];
+    n_all[1] = last[1][0] + last[1][1];
+    n_geno[0] = last[2][0] + last[2][1];
+    n_geno[1] = last[3][0] + last[3][1];
+    if ((unsigned long long)(n_all[0] + n_all[1]) != hc.n_out || (unsigned long long)(n_geno[0] + n_geno[1]) != hc.out_pool)
+      return set_err(GQ_E_ASSERT, "somatic-likelihoods: the groups hold %lld alleles and %lld genotypes, the kernel reserved %llu and %llu",
+                     (long long)(n_all[0] + n_all[1]), (long long)(n_geno[0] + n_geno[1]), hc.n_out, hc.out_pool);
+    lay = sl_layout(ng, n_all, n_geno, (int64_t)std::min<unsigned long long>(hc.pool_used, pool_cap));
+    HIP_TRY(c->image.ensure(lay.bytes));
+    HIP_TRY(hipMemsetAsync(c->image.p, 0, 64, c->stream));
+    const unsigned pb = (unsigned)std::min<int64_t>((ng + kSomWaves - 1) / kSomWaves, (int64_t)32 * c->n_cu);
+    hipLaunchKernelGGL(sl_place, dim3(pb), dim3(kBlock), 0, c->stream, (const SlGroup *)c->srecs.p,
+                       (const uint32_t *)order, off, (const GlAllele *)c->recs.p, (const double *)c->recs_sorted.p,
+                       (const uint8_t *)c->pool.p, ng, lay, (uint8_t *)c->image.p);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(c->image.ensure(lay.bytes));
+    HIP_TRY(hipMemsetAsync(c->image.p, 0, 64, c->stream));
+  }
+  HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+  uint8_t *blk = (uint8_t *)malloc(lay.bytes);
+  if (!blk) return set_err(GQ_E_NOMEM, "somatic-likelihoods result block of %zu bytes", lay.bytes);
+  res->block_ = blk;
+  HIP_TRY(hipMemcpyAsync(blk, c->image.p, lay.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const auto m0 = std::chrono::steady_clock::now();
+  if (((const int64_t *)blk)[1] != 0)
+    return set_err(GQ_E_ASSERT, "somatic-likelihoods: %lld groups disagree with their recorded sizes",
+                   (long long)((const int64_t *)blk)[1]);
+  res->n_groups = ng;
+  res->contig = (int32_t *)(blk + lay.contig);
+  res->pos = (int64_t *)(blk + lay.pos);
+  res->flags = blk + lay.flags;
+  res->tumor_ref_base = blk + lay.t_ref_base;
+  res->normal_ref_base = blk + lay.n_ref_base;
+  res->tumor_depth = (int32_t *)(blk + lay.t_depth);
+  res->normal_depth = (int32_t *)(blk + lay.n_depth);
+  res->tumor_n_alleles = (int32_t *)(blk + lay.t_n_alleles);
+  res->normal_n_alleles = (int32_t *)(blk + lay.n_n_alleles);
+  res->tumor_allele_first = (int64_t *)(blk + lay.t_allele_first);
+  res->normal_allele_first = (int64_t *)(blk + lay.n_allele_first);
+  res->tumor_geno_first = (int64_t *)(blk + lay.t_geno_first);
+  res->normal_geno_first = (int64_t *)(blk + lay.n_geno_first);
+  res->best = (int32_t *)(blk + lay.best);
+  res->has_variant = blk + lay.has_variant;
+  res->normal_variant_total = (double *)(blk + lay.var_total);
+  res->log_odds = (double *)(blk + lay.log_odds);
+  res->n_tumor_alleles = n_all[0];
+  res->tumor_ref_off = (int64_t *)(blk + lay.a_ref_off[0]);
+  res->tumor_ref_len = (int32_t *)(blk + lay.a_ref_len[0]);
+  res->tumor_alt_off = (int64_t *)(blk + lay.a_alt_off[0]);
+  res->tumor_alt_len = (int32_t *)(blk + lay.a_alt_len[0]);
+  res->tumor_allele_depth = (int32_t *)(blk + lay.a_depth[0]);
+  res->n_normal_alleles = n_all[1];
+  res->normal_ref_off = (int64_t *)(blk + lay.a_ref_off[1]);
+  res->normal_ref_len = (int32_t *)(blk + lay.a_ref_len[1]);
+  res->normal_alt_off = (int64_t *)(blk + lay.a_alt_off[1]);
+  res->normal_alt_len = (int32_t *)(blk + lay.a_alt_len[1]);
+  res->normal_allele_depth = (int32_t *)(blk + lay.a_depth[1]);
+  res->allele_pool = blk + lay.pool;
+  res->pool_len = ng > 0 ? *(const int64_t *)blk : 0;
+  res->n_tumor_genotypes = n_geno[0];
+  res->tumor_log_likelihood = (double *)(blk + lay.ll[0]);
+  res->n_normal_genotypes = n_geno[1];
+  res->normal_log_likelihood = (double *)(blk + lay.ll[1]);
+  res->visited_loci = (int64_t)hc.visited;
+  res->listed_loci = (int64_t)n_cand;
+  res->block_bytes = (int64_t)lay.bytes;
+  c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timings.pileup_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+  c->timings.complex_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
+  c->timings.finalize_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
+  c->timings.walk_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
+  c->timings.total_ms = ms;
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = pt.n_tiles;
+  c->timings.walk_tiles = (int64_t)hc.n_slow;
+  c->timings.deep_loci = (int64_t)hc.n_deep;
+  c->timings.deep_max = (int64_t)hc.deep_max;
+  c->timings.deep_ms = deep_ms;
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  return GQ_OK;
+}
+}  // namespace
+
+// timings: pileup_ms the list (candidate pass with the bound off + cand_prep), complex_ms the
+// per-locus kernels (heap-order round trip included; deep_ms the deep / wide launches inside it,
+// deep_loci what they took), finalize_ms ordering, scans and placement, walk_ms the device-to-host
+// copy of the block, marshal_ms the host time after it.
+gq_status gq_somatic_likelihoods_call(gq_ctx *c, const gq_dev_reads *t, const gq_dev_reads *n, const gq_loci *loci,
+                                      const gq_somatic_likelihood_params *p, gq_somatic_likelihoods **out) {
+  if (!c || !t || !n || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_somatic_likelihoods_call: null argument");
+  if (t->d.n_contigs != n->d.n_contigs)
+    return set_err(GQ_E_ARG, "tumor and normal read sets must share the contig list (%d vs %d contigs)",
+                   t->d.n_contigs, n->d.n_contigs);
+  HIP_TRY(hipSetDevice(c->device));
+  for (const gq_dev_reads *s : {t, n}) {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(s);
+    if (vs) return vs;
+  }
+  gq_somatic_likelihoods *res = (gq_somatic_likelihoods *)calloc(1, sizeof(gq_somatic_likelihoods));
+  if (!res) return set_err(GQ_E_NOMEM, "calloc");
+  const gq_status st = somatic_likelihoods_run(c, t, n, loci, p, res);
+  if (st) {
+    gq_free_somatic_likelihoods(res);
+    return st;
+  }
+  *out = res;
+  return GQ_OK;
+}
+
+void gq_free_somatic_likelihoods(gq_somatic_likelihoods *r) {
   if (!r) return;
   free(r->block_);  // one block holds every array
   free(r);

@@ -151,10 +151,12 @@ struct GenoOut {
 // order (:190-199); maxBy = the first maximum.  The normal's variant mass (with_var_sum) adds
 // the variant genotypes' likelihoods in the iteration order of the immutable Map `toMap`
 // builds (SomaticStandardCaller.scala:206-217): generation order up to four genotypes, the
-// HashTrieMap's beyond (gq_scala_order.h).
+// HashTrieMap's beyond (gq_scala_order.h).  log_out (somatic-likelihoods): each genotype's
+// normalised log-likelihood is stored there as well.
 template <int NS>
 __device__ __forceinline__ GenoOut genotypes_el(const DevReads &R, const Pile<NS> &P, const uint4 *el, int n_el, int32_t pos,
-                                                bool include_alignment, bool with_var_sum, CallMem &m, Counters *ctr) {
+                                                bool include_alignment, bool with_var_sum, CallMem &m, Counters *ctr,
+                                                double *log_out = nullptr) {
   const int lane = threadIdx.x & 63;
   GenoOut res{};
   const uint64_t cyc0 = __builtin_readcyclecounter();
@@ -269,6 +271,7 @@ __device__ __forceinline__ GenoOut genotypes_el(const DevReads &R, const Pile<NS
     const int g = g0 + lane;
     double L = 0.0;
     if (g < G) {
+      if (log_out) log_out[g] = m.ll[g] - lt;  // (somatic-likelihoods: the log-space value, Likelihood.scala:193)
       L = sm::exp(m.ll[g] - lt);
       m.ll[g] = L;  // the normalised likelihood, for the variant mass below
     }

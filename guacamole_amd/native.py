@@ -197,6 +197,34 @@ class gq_pileup_elements(C.Structure):
                 ("block_", C.c_void_p)]
 
 
+class gq_somatic_likelihood_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("filter_multi_allelic", C.c_int32), ("max_read_depth", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def _sample_allele_fields(s: str):
+    return [(s + "_ref_off", C.POINTER(C.c_int64)), (s + "_ref_len", C.POINTER(C.c_int32)),
+            (s + "_alt_off", C.POINTER(C.c_int64)), (s + "_alt_len", C.POINTER(C.c_int32)),
+            (s + "_allele_depth", C.POINTER(C.c_int32))]
+
+
+class gq_somatic_likelihoods(C.Structure):
+    _fields_ = ([("n_groups", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int64)),
+                 ("flags", C.POINTER(C.c_uint8)), ("tumor_ref_base", C.POINTER(C.c_uint8)),
+                 ("normal_ref_base", C.POINTER(C.c_uint8)), ("tumor_depth", C.POINTER(C.c_int32)),
+                 ("normal_depth", C.POINTER(C.c_int32)), ("tumor_n_alleles", C.POINTER(C.c_int32)),
+                 ("normal_n_alleles", C.POINTER(C.c_int32)), ("tumor_allele_first", C.POINTER(C.c_int64)),
+                 ("normal_allele_first", C.POINTER(C.c_int64)), ("tumor_geno_first", C.POINTER(C.c_int64)),
+                 ("normal_geno_first", C.POINTER(C.c_int64)), ("best", C.POINTER(C.c_int32)),
+                 ("has_variant", C.POINTER(C.c_uint8)), ("normal_variant_total", C.POINTER(C.c_double)),
+                 ("log_odds", C.POINTER(C.c_double)), ("n_tumor_alleles", C.c_int64)] + _sample_allele_fields("tumor") +
+                [("n_normal_alleles", C.c_int64)] + _sample_allele_fields("normal") +
+                [("allele_pool", C.POINTER(C.c_uint8)), ("pool_len", C.c_int64), ("n_tumor_genotypes", C.c_int64),
+                 ("tumor_log_likelihood", C.POINTER(C.c_double)), ("n_normal_genotypes", C.c_int64),
+                 ("normal_log_likelihood", C.POINTER(C.c_double)), ("visited_loci", C.c_int64),
+                 ("listed_loci", C.c_int64), ("block_bytes", C.c_int64), ("block_", C.c_void_p)])
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -210,7 +238,8 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_bam_dev_reads", "gq_reads_positions", "gq_reads_contig_begin", "gq_reads_download", "gq_bam_dev_map",
             "gq_bam_dev_load", "gq_bam_dev_map_ex", "gq_bam_dev_plan", "gq_bam_dev_plan_segments",
             "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
-            "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements")
+            "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements",
+            "gq_somatic_likelihoods_call", "gq_free_somatic_likelihoods")
 
 
 def lib():
@@ -229,7 +258,7 @@ def lib():
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
                   "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call",
-                  "gq_pileup_elements_call"):
+                  "gq_pileup_elements_call", "gq_somatic_likelihoods_call"):
             getattr(L, f).restype = C.c_int
         L.gq_germline_threshold.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_params),
                                             C.POINTER(C.POINTER(gq_calls))]
@@ -262,6 +291,11 @@ def lib():
                                               C.POINTER(C.POINTER(gq_pileup_elements))]
         L.gq_free_pileup_elements.argtypes = [C.POINTER(gq_pileup_elements)]
         L.gq_free_pileup_elements.restype = None
+        L.gq_somatic_likelihoods_call.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gq_loci),
+                                                  C.POINTER(gq_somatic_likelihood_params),
+                                                  C.POINTER(C.POINTER(gq_somatic_likelihoods))]
+        L.gq_free_somatic_likelihoods.argtypes = [C.POINTER(gq_somatic_likelihoods)]
+        L.gq_free_somatic_likelihoods.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -529,6 +563,21 @@ class Context:
             return PileupElements.from_struct(out.contents)
         finally:
             lib().gq_free_pileup_elements(out)
+
+    def somatic_likelihoods(self, tumor: "DeviceReads", normal: "DeviceReads", loci, min_mapq: int = 1,
+                            filter_multi_allelic: bool = False,
+                            max_read_depth: int = 2 ** 31 - 1) -> "SomaticLikelihoods":
+        """gq_somatic_likelihoods_call: both samples' normalised genotype log-likelihoods, the most
+        likely tumor genotype, the normal's variant mass and the somatic log-odds at every locus that
+        passes somatic-standard's gate (before it keeps one allele and applies --odds)."""
+        L, keep = make_gq_loci(*loci)
+        prm = gq_somatic_likelihood_params(int(min_mapq), int(bool(filter_multi_allelic)), int(max_read_depth), 0)
+        out = C.POINTER(gq_somatic_likelihoods)()
+        _check(lib().gq_somatic_likelihoods_call(self.h, tumor.h, normal.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return SomaticLikelihoods.from_struct(out.contents)
+        finally:
+            lib().gq_free_somatic_likelihoods(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:
@@ -912,6 +961,77 @@ class GenotypeLikelihoods:
                             for (i, j), v in zip(pairs, g["log_likelihoods"]))
             self._rows = rows
         return self._rows
+
+
+class SomaticLikelihoods:
+    """gq_somatic_likelihoods_call's result in output order: numpy columns copied out of the
+    library's block (per group = locus, per tumor / normal allele, per tumor / normal genotype),
+    dicts built on first use of ``groups``."""
+
+    GROUP_COLUMNS = ("contig", "pos", "flags", "tumor_ref_base", "normal_ref_base", "tumor_depth", "normal_depth",
+                     "tumor_n_alleles", "normal_n_alleles", "tumor_allele_first", "normal_allele_first",
+                     "tumor_geno_first", "normal_geno_first", "best", "has_variant", "normal_variant_total", "log_odds")
+    ALLELE_COLUMNS = ("ref_off", "ref_len", "alt_off", "alt_len", "allele_depth")
+
+    def __init__(self, cols: Dict[str, np.ndarray], pool: bytes, visited: int, listed: int, block_bytes: int = 0):
+        self.cols, self.pool, self.visited_loci, self.listed_loci = cols, pool, visited, listed
+        self.block_bytes = block_bytes
+        self._groups: Optional[List[dict]] = None
+
+    @staticmethod
+    def from_struct(c: gq_somatic_likelihoods) -> "SomaticLikelihoods":
+        def col(name: str, n: int) -> np.ndarray:
+            dt = np.dtype(getattr(c, name)._type_)
+            if not n:
+                return np.zeros(0, dt)
+            buf = (C.c_uint8 * (n * dt.itemsize)).from_address(C.cast(getattr(c, name), C.c_void_p).value)
+            return np.frombuffer(buf, dtype=dt, count=n).copy()
+        cols = {k: col(k, int(c.n_groups)) for k in SomaticLikelihoods.GROUP_COLUMNS}
+        for s, na, ng in (("tumor", c.n_tumor_alleles, c.n_tumor_genotypes),
+                          ("normal", c.n_normal_alleles, c.n_normal_genotypes)):
+            cols.update({s + "_" + k: col(s + "_" + k, int(na)) for k in SomaticLikelihoods.ALLELE_COLUMNS})
+            cols[s + "_log_likelihood"] = col(s + "_log_likelihood", int(ng))
+        pool = C.string_at(c.allele_pool, c.pool_len) if c.pool_len else b""
+        return SomaticLikelihoods(cols, pool, int(c.visited_loci), int(c.listed_loci), int(c.block_bytes))
+
+    def __len__(self) -> int:
+        return int(self.cols["pos"].shape[0])
+
+    @property
+    def n_genotypes(self) -> int:
+        return int(self.cols["tumor_log_likelihood"].shape[0] + self.cols["normal_log_likelihood"].shape[0])
+
+    @property
+    def groups(self) -> List[dict]:
+        """dict(contig (index), locus, flags, tumor_ref_base, normal_ref_base, tumor_depth,
+        normal_depth, tumor_alleles / normal_alleles = [(ref, alt, depth)] in Allele order,
+        tumor_log_likelihoods / normal_log_likelihoods = [...] row-major over the allele pairs
+        i <= j, best (index into tumor_log_likelihoods), has_variant, normal_variant_total,
+        log_odds)."""
+        if self._groups is None:
+            c, pool = self.cols, self.pool
+            G = {k: c[k].tolist() for k in self.GROUP_COLUMNS}
+            side = {}
+            for s in ("tumor", "normal"):
+                A = {k: c[s + "_" + k].tolist() for k in self.ALLELE_COLUMNS}
+                al = [(pool[ro:ro + rl].decode("latin-1"), pool[ao:ao + an].decode("latin-1"), d)
+                      for ro, rl, ao, an, d in zip(A["ref_off"], A["ref_len"], A["alt_off"], A["alt_len"],
+                                                   A["allele_depth"])]
+                side[s] = (al, c[s + "_log_likelihood"].tolist())
+            (ta, tl), (na, nl) = side["tumor"], side["normal"]
+            self._groups = [
+                dict(contig=G["contig"][k], locus=G["pos"][k], flags=G["flags"][k],
+                     tumor_ref_base=chr(G["tumor_ref_base"][k]), normal_ref_base=chr(G["normal_ref_base"][k]),
+                     tumor_depth=G["tumor_depth"][k], normal_depth=G["normal_depth"][k],
+                     tumor_alleles=ta[taf:taf + tn], normal_alleles=na[naf:naf + nn],
+                     tumor_log_likelihoods=tl[tgf:tgf + tn * (tn + 1) // 2],
+                     normal_log_likelihoods=nl[ngf:ngf + nn * (nn + 1) // 2],
+                     best=G["best"][k], has_variant=bool(G["has_variant"][k]),
+                     normal_variant_total=G["normal_variant_total"][k], log_odds=G["log_odds"][k])
+                for k, (tn, nn, taf, naf, tgf, ngf) in enumerate(zip(
+                    G["tumor_n_alleles"], G["normal_n_alleles"], G["tumor_allele_first"], G["normal_allele_first"],
+                    G["tumor_geno_first"], G["normal_geno_first"]))]
+        return self._groups
 
 
 class PileupElements:

@@ -616,6 +616,69 @@ gq_status gq_somatic_standard_ref(gq_ctx *ctx, const gq_dev_reads *tumor, const 
                                   const gq_loci *loci, const gq_reference *ref, const gq_somatic_params *params,
                                   gq_somatic_calls **out);
 
+/* somatic-likelihoods: what SomaticStandard.Caller.findPotentialVariantAtLocus
+ * (commands/SomaticStandardCaller.scala:162-245) computes before it keeps one allele per locus and
+ * applies --odds, so that a host can apply its own somatic rule.  One group per locus that
+ * pileupFlatMapTwoRDDs(tumor, normal, partitions, skipEmpty = true) visits, in call order, where the
+ * caller's gate (:184-190) passes after PileupFilter(filter_multi_allelic, min_mapq,
+ * minEdgeDistance = 0) on each pileup: both filtered pileups non-empty, both depths <=
+ * max_read_depth, tumor referenceDepth != depth, and the tumor has an eligible allele (:200).  Each
+ * sample's reference base is its own unfiltered pileup's (MD-derived; no gq_reference here).
+ * A sample's alleles are its eligible alleles (Likelihood.scala:106) in Allele order, each with its
+ * filtered element count; its n (n + 1) / 2 genotypes (i <= j) row-major hold the normalised
+ * log-likelihoods (normalize = true, log space): the tumor's with
+ * probabilityCorrectIncludingAlignment, the normal's with probabilityCorrectIgnoringAlignment (the
+ * normal's at every group; the reference forces them only when has_variant).  best = the first
+ * maximum of exp(tumor log-likelihood) (maxBy, :203); has_variant = that genotype's
+ * hasVariantAllele; normal_variant_total = the normal's variant genotypes' likelihoods added in the
+ * iteration order of the Map `toMap` builds (:206-217); log_odds = log(exp(tumor_ll[best]) /
+ * normal_variant_total) (:218, :236; +inf where the normal has no variant genotype).
+ * flags bit0 / bit1: the tumor / normal reference base came from heap order (bit0 as
+ * gq_somatic_standard's record flag).  Capacities are gq_somatic_standard's: 1024 distinct alleles
+ * per sample, 256 eligible normal alleles (the variant mass ranks every normal genotype), the
+ * heap-order replay's limit; past them GQ_E_CAPACITY.  Every array lives in one block (block_),
+ * filled by one device-to-host copy.                                                            */
+typedef struct {
+  int32_t min_mapq;             /* --min-mapq (1)                                   */
+  int32_t filter_multi_allelic; /* --filter-multi-allelic                           */
+  int32_t max_read_depth;       /* the caller's maxReadDepth (Int.MaxValue)          */
+  int32_t reserved;             /* 0                                                */
+} gq_somatic_likelihood_params;
+typedef struct {
+  int64_t n_groups;            /* loci                                                     */
+  int32_t *contig; int64_t *pos;
+  uint8_t *flags;
+  uint8_t *tumor_ref_base, *normal_ref_base;
+  int32_t *tumor_depth, *normal_depth;          /* filtered depths                         */
+  int32_t *tumor_n_alleles, *normal_n_alleles;  /* eligible alleles n: n(n+1)/2 genotypes  */
+  int64_t *tumor_allele_first, *normal_allele_first;  /* into the samples' allele columns  */
+  int64_t *tumor_geno_first, *normal_geno_first;      /* into the samples' log-likelihoods */
+  int32_t *best;               /* index among the group's tumor genotypes                  */
+  uint8_t *has_variant;
+  double *normal_variant_total, *log_odds;
+  int64_t n_tumor_alleles;
+  int64_t *tumor_ref_off; int32_t *tumor_ref_len; int64_t *tumor_alt_off; int32_t *tumor_alt_len;
+  int32_t *tumor_allele_depth;
+  int64_t n_normal_alleles;
+  int64_t *normal_ref_off; int32_t *normal_ref_len; int64_t *normal_alt_off; int32_t *normal_alt_len;
+  int32_t *normal_allele_depth;
+  uint8_t *allele_pool; int64_t pool_len;       /* both samples' allele bytes              */
+  int64_t n_tumor_genotypes; double *tumor_log_likelihood;
+  int64_t n_normal_genotypes; double *normal_log_likelihood;
+  int64_t visited_loci;        /* loci where either pileup is not empty                    */
+  int64_t listed_loci;         /* loci handed to the per-locus kernel                      */
+  int64_t block_bytes;         /* bytes of block_ (what the device-to-host copy moved)     */
+  void *block_;
+} gq_somatic_likelihoods;
+#ifdef __cplusplus
+static_assert(sizeof(gq_somatic_likelihood_params) == 16, "gq_somatic_likelihood_params layout");
+static_assert(sizeof(gq_somatic_likelihoods) == 320, "gq_somatic_likelihoods layout");
+#endif
+gq_status gq_somatic_likelihoods_call(gq_ctx *ctx, const gq_dev_reads *tumor, const gq_dev_reads *normal,
+                                      const gq_loci *loci, const gq_somatic_likelihood_params *params,
+                                      gq_somatic_likelihoods **out);
+void gq_free_somatic_likelihoods(gq_somatic_likelihoods *res);
+
 #ifdef __cplusplus
 }
 #endif
