@@ -1080,6 +1080,122 @@ def somatic_likelihoods_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def pileup_counts_reads(ctx: native.Context, rs: ReadSet, loci, chunk_loci: int = 0, **params):
+    """The per-locus count table (gq_pileup_counts_call) at the loci pileupFlatMap(reads, partitions,
+    skipEmpty=true) visits, all samples merged.  params: min_mapq (1), min_depth (1), variants_only
+    (False).  -> native.PileupCounts: numpy columns in call order, ``contig`` indexing its
+    ``contig_names`` (its ``rows`` give the name).  chunk_loci > 0: one library call per run of
+    whole tasks (plan_count_chunks), the same rows."""
+    dr = device_reads(ctx, rs)
+    runs = plan_count_chunks(loci[1], loci[2], loci[3], chunk_loci) if chunk_loci > 0 else []
+    res = native.PileupCounts.concat([ctx.pileup_counts_call(dr, tuple(a[lo:hi] for a in loci), **params)
+                                      for lo, hi in runs or [(0, len(loci[3]))]])
+    res.contig_names = list(rs.contig_names)
+    return res
+
+
+def plan_count_chunks(start, end, task, chunk_loci: int) -> List[tuple]:
+    """Runs [lo, hi) of the flat loci ranges (flatten_partitions: task ascending), one per library
+    call: each run is whole tasks whose loci sum to at most chunk_loci, in order; a task with more
+    loci than that is a run of its own.  A task is never split: its first pileup defines its
+    heap order, so a split would change the rows at heap-order loci."""
+    runs: List[tuple] = []
+    n = len(task)
+    lo, total, k = 0, 0, 0
+    while k < n:
+        j, size = k, 0
+        while j < n and task[j] == task[k]:
+            size += int(end[j]) - int(start[j])
+            j += 1
+        if k > lo and total + size > chunk_loci:
+            runs.append((lo, k))
+            lo, total = k, 0
+        total += size
+        k = j
+    if n > lo:
+        runs.append((lo, n))
+    return runs
+
+
+PILEUP_COUNTS_HEADER = ("contig,locus,refBase,depth,forwardDepth,refDepth,A,C,G,T,N,other,forwardA,forwardC,forwardG,"
+                        "forwardT,forwardN,forwardOther,insertions,deletions,midDeletions,clipped,flags")
+
+
+def write_pileup_counts_csv(path: str, counts: "native.PileupCounts", contig_names: Optional[Sequence[str]] = None,
+                            append: bool = False) -> None:
+    """The rows of pileup_counts_reads as CSV (PILEUP_COUNTS_HEADER), formatted a column at a time.
+    contig_names: the result's own when None.  Refuses an existing path; append=True adds a later
+    call's rows to the file this function made (no header)."""
+    c = counts.cols
+    contig_names = counts.contig_names if contig_names is None else contig_names
+    with open(path, "a" if append else "x") as fh:
+        if not append:
+            fh.write(PILEUP_COUNTS_HEADER + "\n")
+        step = 1 << 20
+        for lo in range(0, len(counts), step):
+            sl = slice(lo, lo + step)
+            names = np.asarray(list(contig_names), dtype=object)[c["contig"][sl]]
+            cols = [names, c["pos"][sl].astype(str), c["ref_base"][sl].astype(np.uint8).view("S1").astype(str)]
+            cols += [c[k][sl].astype(str) for k in ("depth", "forward_depth", "ref_depth")]
+            for k in ("base_count", "base_forward", "kind_count"):
+                cols += [c[k][sl, j].astype(str) for j in range(c[k].shape[1])]
+            cols.append(c["flags"][sl].astype(str))
+            fh.write("".join(",".join(r) + "\n" for r in zip(*cols)))
+
+
+def pileup_counts_main(argv: Sequence[str]) -> int:
+    """pileup-counts: depth, strand-split base counts and element-kind counts at every visited locus
+    of one BAM, as CSV.  Input filters as germline-standard's (GermlineStandardCaller.scala:53-54)."""
+    import os
+    p = argparse.ArgumentParser(prog="pileup-counts",
+                                description="per-locus depth, strand-split A/C/G/T/N/other counts and insertion / "
+                                            "deletion / mid-deletion / clipped counts")
+    p.add_argument("--reads", required=True)
+    p.add_argument("--out", required=True, help="Output CSV path (must not exist)")
+    p.add_argument("--loci", default="", help="Loci to visit (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    p.add_argument("--min-mapq", type=int, default=1, help="Minimum read mapping quality for a read (Phred-scaled)")
+    p.add_argument("--min-depth", type=int, default=1, help="Only loci with at least this many kept elements")
+    p.add_argument("--variants-only", action="store_true", help="Only loci with a non-Match element after the filter")
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    p.add_argument("--chunk-loci", type=int, default=1 << 24,
+                   help="Loci per library call (whole tasks; a larger task goes alone)")
+    args = p.parse_args(argv)
+    single_process_only("pileup-counts")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    if args.chunk_loci < 1:
+        raise ValueError("--chunk-loci must be at least 1")
+    builder = _loci_builder(args)
+    filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
+    ctx = None
+    rs = None
+    if device_ingest(args, args.reads):
+        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
+        ctx = native.Context(args.device)
+        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
+    if rs is None:
+        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    loci = builder.result(rs.contig_lengths_map)
+    parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
+    flat = flatten_partitions(parts, rs.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    dr = device_reads(ctx, rs)
+    n_rows, first = 0, True
+    for lo, hi in plan_count_chunks(flat[1], flat[2], flat[3], args.chunk_loci) or [(0, len(flat[3]))]:
+        res = ctx.pileup_counts_call(dr, tuple(a[lo:hi] for a in flat), min_mapq=args.min_mapq,
+                                     min_depth=args.min_depth, variants_only=args.variants_only)
+        write_pileup_counts_csv(args.out, res, rs.contig_names, append=not first)
+        n_rows, first = n_rows + len(res), False
+    print("Wrote %d pileup count rows." % n_rows, file=sys.stderr)
+    return 0
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -1093,7 +1209,7 @@ def warn_default_parallelism(args, world: int) -> None:
 
 def single_process_only(command: str) -> None:
     """germline-standard, variant-support, vaf-histogram, allele-evidence, genotype-likelihoods,
-    pileup-elements and somatic-likelihoods run as one process on --device: under torch.distributed.run
+    pileup-elements, somatic-likelihoods and pileup-counts run as one process on --device: under torch.distributed.run
     every rank would repeat the whole job and write the same output, so a multi-rank launch is refused."""
     import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -1118,7 +1234,8 @@ def _finish_rank(rc: int) -> int:
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
-            "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main}
+            "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
+            "pileup-counts": pileup_counts_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -1256,6 +1256,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
 #include "gq_allele_evidence.h"
 #include "gq_genotype_likelihoods.h"
 #include "gq_pileup_elements.h"
+#include "gq_pileup_counts.h"
 #include "gq_somatic_likelihoods.h"
 
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
@@ -3079,6 +3080,226 @@ gq_status gq_pileup_elements_call(gq_ctx *c, const gq_dev_reads *rd, const gq_lo
 }
 
 void gq_free_pileup_elements(gq_pileup_elements *r) {
+  if (!r) return;
+  free(r->block_);  // one block holds every array
+  free(r);
+}
+
+namespace {
+PcLayout pc_layout(int64_t n_rows) {
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t N = (size_t)n_rows;
+  PcLayout L;
+  L.contig = 0;
+  L.pos = al(L.contig + 4 * N);
+  L.ref_base = al(L.pos + 8 * N);
+  L.flags = al(L.ref_base + N);
+  L.depth = al(L.flags + N);
+  L.forward_depth = al(L.depth + 4 * N);
+  L.ref_depth = al(L.forward_depth + 4 * N);
+  L.base_count = al(L.ref_depth + 4 * N);
+  L.base_forward = al(L.base_count + 24 * N);
+  L.kind_count = al(L.base_forward + 24 * N);
+  L.bytes = al(L.kind_count + 16 * N + 1);
+  return L;
+}
+// The call into `res` (zeroed; the caller frees it, block included, when this fails).
+gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_pileup_counts_params *p,
+                            gq_pileup_count_rows *res) {
+  const auto h0 = std::chrono::steady_clock::now();
+  c->timings = gq_timings{};
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  Plan pl;
+  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
+  if (st) return st;
+  st = plan(c, rd, loci, kPcT, pl, c->tiles);
+  if (st) return st;
+  if (pl.n_tiles == 0) return GQ_OK;
+  if (pl.n_tiles >= (int64_t)INT32_MAX) return set_err(GQ_E_CAPACITY, "pileup-counts: %lld tiles", (long long)pl.n_tiles);
+  // the tiles a read overlaps, numbered in call order: each takes kPcT rows of the staging array
+  HIP_TRY(c->idx.ensure((size_t)pl.n_tiles * sizeof(uint32_t)));
+  HIP_TRY(c->idx_sorted.ensure((size_t)pl.n_tiles * sizeof(uint32_t)));
+  uint32_t *tslot = (uint32_t *)c->idx_sorted.p;
+  uint32_t n_active = 0;
+  {
+    uint32_t *active = (uint32_t *)c->idx.p;
+    hipLaunchKernelGGL(pileup_counts_active, dim3((unsigned)((pl.n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       c->stream, (const Tile *)c->tiles.p, pl.n_tiles, active);
+    HIP_TRY(hipGetLastError());
+    size_t tmp = 0;
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, active, tslot, (int)pl.n_tiles, c->stream));
+    HIP_TRY(c->sort_tmp.ensure(tmp));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->sort_tmp.p, tmp, active, tslot, (int)pl.n_tiles, c->stream));
+    HIP_TRY(hipMemcpyAsync(&n_active, tslot + (pl.n_tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  if (n_active == 0) return GQ_OK;  // no read overlaps the loci
+  const int64_t n_loci = (int64_t)n_active * kPcT;  // staging rows
+  if (n_loci >= (int64_t)INT32_MAX)
+    return set_err(GQ_E_CAPACITY, "pileup-counts: %lld covered loci in one call (call it over runs of whole tasks)",
+                   (long long)n_loci);
+  // a buffer that overflowed is grown to what the pass needed and the pass repeated (the staging
+  // array is rewritten from the start: every pass stores the same rows)
+  enum { B_ITEM, B_AMB, B_N };
+  int grown[B_N] = {};
+  bool spent = false;
+  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
+    if (need <= cap) return false;
+    if (++grown[which] > 2) spent = true;
+    cap = need + slack;
+    return true;
+  };
+  SomWin sw{};
+  st = build_somwin(c, pl, rd, rd, sw);
+  if (st) return st;
+  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+    c->n_cu = 256;
+  // the dense staging: a row, a keep word and its scanned position per locus of those tiles
+  HIP_TRY(c->recs.ensure((size_t)n_loci * sizeof(PcRow)));
+  HIP_TRY(c->keys.ensure((size_t)n_loci * sizeof(uint32_t)));
+  HIP_TRY(c->keys_sorted.ensure((size_t)n_loci * sizeof(uint32_t)));
+  PcRow *rows = (PcRow *)c->recs.p;
+  uint32_t *keep = (uint32_t *)c->keys.p, *inc = (uint32_t *)c->keys_sorted.p;
+  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(n_loci, std::max<int64_t>(n_loci / 8, 1 << 16)),
+                     amb_cap = 4096;
+  Counters hc{};
+  Counters *ctr = nullptr;
+  int64_t n_items = 0;
+  for (;;) {
+    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
+    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
+    HIP_TRY(c->counters.ensure(sizeof(Counters)));
+    ctr = (Counters *)c->counters.p;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+    HIP_TRY(hipMemsetAsync(keep, 0, (size_t)n_loci * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    hipLaunchKernelGGL((pileup_counts_tile<kPcT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
+                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, *p,
+                       (const uint32_t *)tslot, rows, keep, n_loci, (ComplexItem *)c->cplx.p, item_cap, ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hc.err) break;
+    if (grow(B_ITEM, item_cap, hc.n_complex, 1024)) {
+      if (spent) return set_err(GQ_E_CAPACITY, "pileup-counts: locus list capacity retries exhausted");
+      continue;
+    }
+    n_items = (int64_t)hc.n_complex;
+    if (n_items == 0) break;
+    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
+    hipLaunchKernelGGL(pileup_counts_locus, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p,
+                       (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, (const uint32_t *)tslot, rows, keep, n_loci,
+                       ctr, sw, (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hc.err) break;
+    if (grow(B_AMB, amb_cap, hc.n_amb, 1024)) {
+      if (spent) return set_err(GQ_E_CAPACITY, "pileup-counts: heap-order list capacity retries exhausted");
+      continue;
+    }
+    if (hc.n_amb > 0) {  // heap-order reference bases: replay, then those loci again
+      std::vector<AmbItem> amb((size_t)hc.n_amb);
+      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(c->amb_ref.ensure(amb.size()));
+      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
+      if (st) return st;
+      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
+      hipLaunchKernelGGL(pileup_counts_locus, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
+                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p,
+                         (const uint32_t *)tslot, rows, keep, n_loci, ctr, sw, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
+                         (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    }
+    break;
+  }
+  // ---- the keep words scanned to positions; the total sizes the result block
+  size_t tmp = 0;
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, keep, inc, (int)n_loci, c->stream));
+  HIP_TRY(c->sort_tmp.ensure(tmp));
+  if (!hc.err) HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->sort_tmp.p, tmp, keep, inc, (int)n_loci, c->stream));
+  uint32_t n_rows32 = 0;
+  if (!hc.err) HIP_TRY(hipMemcpyAsync(&n_rows32, inc + (n_loci - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));  // (the second pass' errors)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  st = check_device_error(c, hc);
+  if (st) return st;
+  const int64_t n_rows = (int64_t)n_rows32;
+  const PcLayout lay = pc_layout(n_rows);
+  HIP_TRY(c->image.ensure(lay.bytes));
+  if (n_rows > 0) {
+    hipLaunchKernelGGL(pileup_counts_gather, dim3((unsigned)((n_loci + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       (const PcRow *)rows, (const uint32_t *)keep, (const uint32_t *)inc, n_loci, n_rows, lay,
+                       (uint8_t *)c->image.p);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+  uint8_t *blk = (uint8_t *)malloc(lay.bytes);
+  if (!blk) return set_err(GQ_E_NOMEM, "pileup-counts result block of %zu bytes", lay.bytes);
+  res->block_ = blk;
+  if (n_rows > 0) HIP_TRY(hipMemcpyAsync(blk, c->image.p, lay.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  res->n = n_rows;
+  res->contig = (int32_t *)(blk + lay.contig);
+  res->pos = (int64_t *)(blk + lay.pos);
+  res->ref_base = blk + lay.ref_base;
+  res->flags = blk + lay.flags;
+  res->depth = (int32_t *)(blk + lay.depth);
+  res->forward_depth = (int32_t *)(blk + lay.forward_depth);
+  res->ref_depth = (int32_t *)(blk + lay.ref_depth);
+  res->base_count = (int32_t *)(blk + lay.base_count);
+  res->base_forward = (int32_t *)(blk + lay.base_forward);
+  res->kind_count = (int32_t *)(blk + lay.kind_count);
+  res->visited_loci = (int64_t)hc.visited;
+  res->listed_loci = n_items;
+  res->block_bytes = (int64_t)lay.bytes;
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timings.pileup_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+  c->timings.complex_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
+  c->timings.finalize_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
+  c->timings.walk_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
+  c->timings.total_ms = ms;
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = pl.n_tiles;
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  return GQ_OK;
+}
+}  // namespace
+
+// timings: pileup_ms the tile kernel, complex_ms the per-locus kernel (heap-order round trip
+// included), finalize_ms the scan and the gather, walk_ms the device-to-host copy of the block.
+gq_status gq_pileup_counts_call(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci,
+                                const gq_pileup_counts_params *p, gq_pileup_count_rows **out) {
+  if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_pileup_counts_call: null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
+  gq_pileup_count_rows *res = (gq_pileup_count_rows *)calloc(1, sizeof(gq_pileup_count_rows));
+  if (!res) return set_err(GQ_E_NOMEM, "calloc");
+  const gq_status st = pileup_counts_run(c, rd, loci, p, res);
+  if (st) {
+    gq_free_pileup_counts(res);
+    return st;
+  }
+  *out = res;
+  return GQ_OK;
+}
+
+void gq_free_pileup_counts(gq_pileup_count_rows *r) {
   if (!r) return;
   free(r->block_);  // one block holds every array
   free(r);

@@ -225,6 +225,20 @@ class gq_somatic_likelihoods(C.Structure):
                  ("listed_loci", C.c_int64), ("block_bytes", C.c_int64), ("block_", C.c_void_p)])
 
 
+class gq_pileup_counts_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("min_depth", C.c_int32), ("variants_only", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class gq_pileup_count_rows(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int64)),
+                ("ref_base", C.POINTER(C.c_uint8)), ("flags", C.POINTER(C.c_uint8)), ("depth", C.POINTER(C.c_int32)),
+                ("forward_depth", C.POINTER(C.c_int32)), ("ref_depth", C.POINTER(C.c_int32)),
+                ("base_count", C.POINTER(C.c_int32)), ("base_forward", C.POINTER(C.c_int32)),
+                ("kind_count", C.POINTER(C.c_int32)), ("visited_loci", C.c_int64), ("listed_loci", C.c_int64),
+                ("block_bytes", C.c_int64), ("block_", C.c_void_p)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -239,7 +253,8 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_bam_dev_load", "gq_bam_dev_map_ex", "gq_bam_dev_plan", "gq_bam_dev_plan_segments",
             "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
             "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements",
-            "gq_somatic_likelihoods_call", "gq_free_somatic_likelihoods")
+            "gq_somatic_likelihoods_call", "gq_free_somatic_likelihoods", "gq_pileup_counts_call",
+            "gq_free_pileup_counts")
 
 
 def lib():
@@ -258,7 +273,7 @@ def lib():
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
                   "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call",
-                  "gq_pileup_elements_call", "gq_somatic_likelihoods_call"):
+                  "gq_pileup_elements_call", "gq_somatic_likelihoods_call", "gq_pileup_counts_call"):
             getattr(L, f).restype = C.c_int
         L.gq_germline_threshold.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_germline_params),
                                             C.POINTER(C.POINTER(gq_calls))]
@@ -296,6 +311,11 @@ def lib():
                                                   C.POINTER(C.POINTER(gq_somatic_likelihoods))]
         L.gq_free_somatic_likelihoods.argtypes = [C.POINTER(gq_somatic_likelihoods)]
         L.gq_free_somatic_likelihoods.restype = None
+        L.gq_pileup_counts_call.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci),
+                                            C.POINTER(gq_pileup_counts_params),
+                                            C.POINTER(C.POINTER(gq_pileup_count_rows))]
+        L.gq_free_pileup_counts.argtypes = [C.POINTER(gq_pileup_count_rows)]
+        L.gq_free_pileup_counts.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -578,6 +598,20 @@ class Context:
             return SomaticLikelihoods.from_struct(out.contents)
         finally:
             lib().gq_free_somatic_likelihoods(out)
+
+    def pileup_counts_call(self, reads: "DeviceReads", loci, min_mapq: int = 1, min_depth: int = 1,
+                           variants_only: bool = False) -> "PileupCounts":
+        """gq_pileup_counts_call: one row per locus whose filtered pileup has depth >= max(1,
+        min_depth) (variants_only: and depth > ref_depth), in call order: depth, strand-split base
+        counts and element-kind counts.  (``pileup_counts`` is the dense, unfiltered histogram.)"""
+        L, keep = make_gq_loci(*loci)
+        prm = gq_pileup_counts_params(int(min_mapq), int(min_depth), int(bool(variants_only)), 0)
+        out = C.POINTER(gq_pileup_count_rows)()
+        _check(lib().gq_pileup_counts_call(self.h, reads.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return PileupCounts.from_struct(out.contents)
+        finally:
+            lib().gq_free_pileup_counts(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:
@@ -1099,3 +1133,58 @@ class PileupElements:
                             zip(L["contig"], L["pos"], L["ref_base"], L["flags"], L["depth"], L["n_alleles"],
                                 L["elem_first"], L["allele_first"])]
         return self._groups
+
+
+class PileupCounts:
+    """gq_pileup_counts_call's result in call order: numpy columns copied out of the library's block
+    (``base_count`` / ``base_forward`` n x 6 in the order BASES, ``kind_count`` n x 4 in the order
+    KINDS).  No per-row objects are made unless ``rows`` is asked for (small results)."""
+
+    COLUMNS = ("contig", "pos", "ref_base", "flags", "depth", "forward_depth", "ref_depth", "base_count",
+               "base_forward", "kind_count")
+    WIDTH = dict(base_count=6, base_forward=6, kind_count=4)
+    BASES = ("A", "C", "G", "T", "N", "other")
+    KINDS = ("insertions", "deletions", "mid_deletions", "clipped")
+
+    def __init__(self, cols: Dict[str, np.ndarray], visited: int, listed: int, block_bytes: int = 0):
+        self.cols, self.visited_loci, self.listed_loci, self.block_bytes = cols, visited, listed, block_bytes
+        self.contig_names: Optional[List[str]] = None  # set by commands.pileup_counts_reads
+
+    @staticmethod
+    def from_struct(c: gq_pileup_count_rows) -> "PileupCounts":
+        n = int(c.n)
+
+        def col(name: str) -> np.ndarray:
+            dt, w = np.dtype(getattr(c, name)._type_), PileupCounts.WIDTH.get(name, 1)
+            if not n:
+                a = np.zeros(0, dt)
+            else:
+                buf = (C.c_uint8 * (n * w * dt.itemsize)).from_address(C.cast(getattr(c, name), C.c_void_p).value)
+                a = np.frombuffer(buf, dtype=dt, count=n * w).copy()
+            return a.reshape(-1, w) if w > 1 else a
+        return PileupCounts({k: col(k) for k in PileupCounts.COLUMNS}, int(c.visited_loci), int(c.listed_loci),
+                            int(c.block_bytes))
+
+    @staticmethod
+    def concat(parts: Sequence["PileupCounts"]) -> "PileupCounts":
+        """The results of consecutive calls (runs of whole tasks, in call order) as one."""
+        if len(parts) == 1:
+            return parts[0]
+        cols = {k: np.concatenate([p.cols[k] for p in parts]) for k in PileupCounts.COLUMNS}
+        return PileupCounts(cols, sum(p.visited_loci for p in parts), sum(p.listed_loci for p in parts),
+                            sum(p.block_bytes for p in parts))
+
+    def __len__(self) -> int:
+        return int(self.cols["pos"].shape[0])
+
+    @property
+    def rows(self) -> List[dict]:
+        """dict(contig (its name where contig_names is set, else its index), locus, ref_base, flags,
+        depth, forward_depth, ref_depth, base_count, base_forward (tuples in the order BASES),
+        kind_count (tuple in the order KINDS))."""
+        L = {k: self.cols[k].tolist() for k in self.COLUMNS}
+        if self.contig_names is not None:
+            L["contig"] = [self.contig_names[ct] for ct in L["contig"]]
+        return [dict(contig=ct, locus=ps, ref_base=chr(rb), flags=fl, depth=d, forward_depth=fd, ref_depth=rd,
+                     base_count=tuple(bc), base_forward=tuple(bf), kind_count=tuple(kc))
+                for ct, ps, rb, fl, d, fd, rd, bc, bf, kc in zip(*[L[k] for k in self.COLUMNS])]

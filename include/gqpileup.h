@@ -679,6 +679,50 @@ gq_status gq_somatic_likelihoods_call(gq_ctx *ctx, const gq_dev_reads *tumor, co
                                       gq_somatic_likelihoods **out);
 void gq_free_somatic_likelihoods(gq_somatic_likelihoods *res);
 
+/* pileup-counts: the per-locus table of pileupFlatMap(reads, partitions, skipEmpty = true) over
+ * one read set, all samples merged: strand-split base counts and element-kind counts.  Elements of
+ * reads with mapq < min_mapq are dropped first (QualityAlignedReadsFilter); the reference base is
+ * the unfiltered pileup's and the flag bit gq_allele_evidence's.  One row per locus whose filtered
+ * pileup has depth >= max(1, min_depth) (and, with variants_only, depth > ref_depth), in call
+ * order; unlike gq_pileup_counts (dense, unfiltered, one entry per locus of `loci`) the rows are
+ * compacted on the device.  At every row
+ *   depth == sum(base_count) + sum(kind_count),
+ *   ref_depth == base_count[index of ref_base] (N at index 4),
+ *   sum(base_forward) <= forward_depth <= depth.
+ * The call stages 96 bytes of device memory per locus of every 512-locus tile of `loci` a read
+ * overlaps: a caller whose covered loci need more than the device has makes several calls over
+ * whole tasks (a task's first pileup defines its heap order).  Every array lives in one block (block_), filled by one device-to-host copy.
+ * (The result struct cannot take the name of the function gq_pileup_counts.)                   */
+typedef struct {
+  int32_t min_mapq;        /* keep elements with read mapq >= min_mapq; 0 keeps all */
+  int32_t min_depth;       /* rows with depth >= max(1, min_depth)                  */
+  int32_t variants_only;   /* 1: only rows with depth > ref_depth                   */
+  int32_t reserved;        /* 0                                                     */
+} gq_pileup_counts_params;
+typedef struct {
+  int64_t n;                   /* rows                                                     */
+  int32_t *contig; int64_t *pos;
+  uint8_t *ref_base;           /* the (unfiltered) pileup's reference base: A C G T or N   */
+  uint8_t *flags;              /* bit0: reference base from heap order                     */
+  int32_t *depth;              /* kept elements                                            */
+  int32_t *forward_depth;      /* ... of positive-strand reads                             */
+  int32_t *ref_depth;          /* Match elements                                           */
+  int32_t *base_count;         /* [n * 6] Match/Mismatch elements by sequenced base: A C G T N other */
+  int32_t *base_forward;       /* [n * 6] ... of positive-strand reads                     */
+  int32_t *kind_count;         /* [n * 4] Insertion, Deletion, MidDeletion, Clipped elements */
+  int64_t visited_loci;        /* loci whose filtered pileup is not empty                  */
+  int64_t listed_loci;         /* loci handed to the per-locus kernel                      */
+  int64_t block_bytes;         /* bytes of block_ (what the device-to-host copy moved)     */
+  void *block_;
+} gq_pileup_count_rows;
+#ifdef __cplusplus
+static_assert(sizeof(gq_pileup_counts_params) == 16, "gq_pileup_counts_params layout");
+static_assert(sizeof(gq_pileup_count_rows) == 120, "gq_pileup_count_rows layout");
+#endif
+gq_status gq_pileup_counts_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
+                                const gq_pileup_counts_params *params, gq_pileup_count_rows **out);
+void gq_free_pileup_counts(gq_pileup_count_rows *res);
+
 #ifdef __cplusplus
 }
 #endif
