@@ -53,6 +53,9 @@
 #ifndef GQ_DIR_U
 #define GQ_DIR_U 4
 #endif
+#ifndef GQ_DIR_G
+#define GQ_DIR_G 1  // tiles a wave claims at a time from a head word (the tile hand-out)
+#endif
 struct DirCfg {
   static constexpr int kT = 512;       // loci per tile: 64 lanes x 8 loci
   static constexpr int kWaves = 4;     // waves per workgroup, each on its own tiles
@@ -70,7 +73,10 @@ struct DirCfg {
 // no 16-bit widening; event counts in bytes); deeper tiles are listed (deep, ctr->n_deep) for the
 // DEEP instantiation, whose waves take them from the list, widen the counts into 16-bit pairs
 // every 240 slots, and write into the walker's output partitions.
-template <bool DEEP>
+// HAND (DEEP = false only): the waves claim their tiles at run time from the head words (the
+// tile hand-out, below) instead of walking their workgroup's static share; the static
+// instantiation's loop is the plain one.
+template <bool DEEP, bool HAND = false>
 __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_eu(GQ_DIR_WPE))) void germline_direct(
     const Tile *__restrict__ tiles, int64_t n_tiles, DevReads R, int threshold, int emit_ref, int emit_no_call,
     CallRec *__restrict__ recs, ComplexItem *__restrict__ cplx, OutGeom og, Counters *ctr, int32_t *__restrict__ slow,
@@ -137,11 +143,61 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
   auto f32 = [](uint32_t rec, int d) { return (uint32_t)__builtin_amdgcn_readlane((int)rec, d); };
   auto f64 = [&](uint32_t rec, int d) { return (int64_t)((uint64_t)f32(rec, d) | ((uint64_t)f32(rec, d + 1) << 32)); };
   const int32_t colr = 8 * lane;  // this lane's column, relative to the block: loci [B0 + colr, B0 + colr + 8)
-  // DEEP: the listed tiles, a wave at a time over the grid; else this workgroup's run of tiles
+  // DEEP: the listed tiles, a wave at a time over the grid; else this workgroup's run of tiles, a
+  // tile per wave at a time, or (HAND) the hand-out
   const int64_t n_deep = DEEP ? (int64_t)min(ctr->n_deep, (unsigned long long)n_tiles) : 0;
-  const int64_t iend = DEEP ? n_deep : i1, istep = DEEP ? (int64_t)gridDim.x * C::kWaves : C::kWaves;
+  int64_t iend = DEEP ? n_deep : i1, istep = DEEP ? (int64_t)gridDim.x * C::kWaves : C::kWaves;
   int64_t i = DEEP ? (int64_t)blockIdx.x * C::kWaves + wave : i0 + wave;
-  for (; i < iend; i += istep) {
+  // The hand-out: head h (ctr->tile_head[h]) owns the h-th eighth of the tiles and counts how many
+  // of them are claimed.  A WAVE claims GQ_DIR_G consecutive tiles with one returning relaxed
+  // add on the head of its workgroup's XCD label (blockIdx.x & 7), walks them and claims again;
+  // a head found exhausted (a relaxed load first: no add) sends the wave on to the next one, and
+  // eight exhausted heads end it.  The next claim is issued before the group's last tile starts
+  // and consumed after it (`ahead`, lane 0's; every other value of the schedule is wave-uniform,
+  // in scalar registers).  No wave reads what another wrote in this launch: no fence, no flag.
+  static_assert(!(DEEP && HAND), "the deep instantiation walks its list");
+  constexpr bool hand = HAND;
+  int hd = (int)(blockIdx.x & (kTileHeads - 1)), heads_left = kTileHeads;
+  uint32_t ahead = 0;
+  bool claimed = false;
+  auto claim = [&]() {
+    uint32_t k = 0;
+    if (lane == 0)
+      k = __hip_atomic_fetch_add(&ctr->tile_head[hd][0], (unsigned)GQ_DIR_G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return k;
+  };
+  auto next_group = [&]() -> bool {  // the wave's next tiles [i, iend); false: every head is exhausted
+    while (heads_left > 0) {
+      const int64_t lo = (n_tiles * hd) / kTileHeads, n = (n_tiles * (hd + 1)) / kTileHeads - lo;
+      uint32_t k;
+      if (claimed) {
+        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ahead);
+        claimed = false;
+      } else {
+        k = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)__hip_atomic_load(&ctr->tile_head[hd][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if ((int64_t)k < n) k = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim());
+      }
+      if ((int64_t)k < n) {
+        i = lo + k;
+        iend = min(i + GQ_DIR_G, lo + n);
+        return true;
+      }
+      hd = (hd + 1) & (kTileHeads - 1);
+      --heads_left;
+    }
+    return false;
+  };
+  if (hand) {
+    i = iend = 0;
+    istep = 1;
+  }
+  for (;; i += istep) {
+    if (i >= iend && !(hand && next_group())) break;
+    if (hand && i + 1 >= iend) {
+      ahead = claim();
+      claimed = true;
+    }
     const uint64_t t_a = (dbg & 16) ? __builtin_readcyclecounter() : 0;
     const int64_t tid = DEEP ? (int64_t)__builtin_amdgcn_readfirstlane(deep[i]) : i;  // the tile
     // Tile: ordinal0 dw 0-1, rb 2-3, re 4-5, contig 6, L0 7, L1 8

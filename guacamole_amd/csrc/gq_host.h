@@ -41,6 +41,7 @@ constexpr int kSpread = 64;
 constexpr int kPartsCols = 2048;  // [0, 2048): one output partition per germline workgroup
 constexpr int kPartsWalk = 1024;  // then one per walker / complex-kernel wave (modulo)
 constexpr int kParts = kPartsCols + kPartsWalk;  // output partitions (see Counters::part)
+constexpr int kTileHeads = 8;  // head words of the tile hand-out, one per XCD label (blockIdx.x & 7)
 
 struct Counters {  // device-side run counters (one allocation, zeroed per call)
   unsigned long long n_rec;
@@ -73,6 +74,9 @@ struct Counters {  // device-side run counters (one allocation, zeroed per call)
   // every writer on the chip.  part_off = exclusive offsets of the kept counts (part_scan).
   unsigned long long part[2][kParts];
   unsigned long long part_off[2][kParts + 1];
+  // germline_direct<false>'s tile hand-out: head h counts the tiles claimed of the h-th eighth of
+  // the call's tiles, each head on its own 128-byte line (zeroed with the rest on every attempt)
+  alignas(128) unsigned tile_head[kTileHeads][32];
 };
 constexpr size_t kCountersHead = offsetof(Counters, part);
 

@@ -2609,8 +2609,18 @@ static unsigned germline_grid(gq_ctx *c, int64_t tiles, bool direct) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)per_cu * c->n_cu, (int64_t)kPartsCols}));
 }
 
+// How germline_direct<false>'s waves get their tiles on a sparse call's first attempt: the
+// hand-out from head words (1, the default), or with GQ_TILES=static the contiguous static split
+// (0: what dense calls and every later attempt use; A/B, the same records).  Read on every call,
+// so one process can run both.
+static int germline_tile_sched() {
+  const char *m = getenv("GQ_TILES");
+  return m && strcmp(m, "static") == 0 ? 0 : 1;
+}
+
 static gq_status launch_germline(gq_ctx *c, int64_t tiles, const DevReads &R, const gq_germline_params *p,
-                                 CallRec *recs, ComplexItem *cplx, const OutGeom &og, Counters *ctr, bool direct) {
+                                 CallRec *recs, ComplexItem *cplx, const OutGeom &og, Counters *ctr, bool direct,
+                                 int sched) {
   static const int dbg = getenv("GQ_DBG") ? atoi(getenv("GQ_DBG")) : 0;  // diagnostics only
   HIP_TRY(c->slow.ensure((size_t)tiles * sizeof(int32_t)));
   // germline_proj reads the Tile + TileX arrays through one buffer of 128 B per tile
@@ -2619,9 +2629,10 @@ static gq_status launch_germline(gq_ctx *c, int64_t tiles, const DevReads &R, co
     // the shallow instantiation over every tile, then the deep one over the tiles it listed
     // (read on the device: no host round trip; an empty list sends its waves home at once)
     HIP_TRY(c->deep_tiles.ensure((size_t)tiles * sizeof(int32_t)));
-    hipLaunchKernelGGL(germline_direct<false>, dim3((unsigned)og.ncols), dim3(DirCfg::kThreads), 0, c->stream,
-                       (const Tile *)c->tiles.p, tiles, R, p->threshold, p->emit_ref, p->emit_no_call, recs, cplx, og, ctr,
-                       (int32_t *)c->slow.p, (int32_t *)c->deep_tiles.p, dbg);
+    const auto shallow = sched ? germline_direct<false, true> : germline_direct<false, false>;  // hand-out | static split
+    hipLaunchKernelGGL(shallow, dim3((unsigned)og.ncols),
+                       dim3(DirCfg::kThreads), 0, c->stream, (const Tile *)c->tiles.p, tiles, R, p->threshold, p->emit_ref,
+                       p->emit_no_call, recs, cplx, og, ctr, (int32_t *)c->slow.p, (int32_t *)c->deep_tiles.p, dbg);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(germline_direct<true>, dim3((unsigned)std::min<int64_t>((tiles + DirCfg::kWaves - 1) / DirCfg::kWaves, 512)),
                        dim3(DirCfg::kThreads), 0, c->stream, (const Tile *)c->tiles.p, tiles, R, p->threshold,
@@ -2733,7 +2744,13 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
     memcpy(&hc, c->pin, kCountersHead);
     return GQ_OK;
   };
-  for (int attempt = 0; attempt < 3; ++attempt) {
+  // A sparse call's first attempt hands the tiles out at run time: a workgroup may then take
+  // more tiles than its static share, and how many differs from run to run.  Every later attempt
+  // uses the static split, whose partition counts repeat, and an attempt 0 that overflowed a
+  // partition under the hand-out is not counted against the three attempts (max_attempts).
+  int max_attempts = 3;
+  for (int attempt = 0; attempt < max_attempts; ++attempt) {
+    const int sched = direct && !dense && attempt == 0 ? germline_tile_sched() : 0;
     HIP_TRY(c->amb.ensure(2 * amb_cap * sizeof(AmbItem)));  // heap-order loci, then order-dependent loci
     const size_t cap_rec = (size_t)og.total(0);
     HIP_TRY(c->recs.ensure(cap_rec * sizeof(CallRec)));
@@ -2751,7 +2768,7 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
     Counters *ctr = (Counters *)c->counters.p;
     HIP_TRY(hipMemsetAsync(ctr, 0, fin_off + 4 * fin_words, c->stream));
     if (attempt == 0) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    st = launch_germline(c, pl.n_tiles, rd->d, p, (CallRec *)c->recs.p, (ComplexItem *)c->cplx.p, og, ctr, direct);
+    st = launch_germline(c, pl.n_tiles, rd->d, p, (CallRec *)c->recs.p, (ComplexItem *)c->cplx.p, og, ctr, direct, sched);
     if (st) {
       free(res);
       return st;
@@ -2825,6 +2842,7 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
         og.capA[w] += hc.part_max[w] + 64;
         og.capB[w] += hc.part_max[w] + 64;
         retry = true;
+        if (sched != 0) max_attempts = 4;
       }
     if (hc.pool_used > pool_cap) {
       pool_cap = hc.pool_used + 4096;
@@ -2892,6 +2910,7 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
         og.capA[0] += hc.part_max[0] + 64;
         og.capB[0] += hc.part_max[0] + 64;
         retry = true;
+        if (sched != 0) max_attempts = 4;
       }
       if (hc.pool_used > pool_cap) {
         pool_cap = hc.pool_used + 4096;
@@ -2914,7 +2933,7 @@ static gq_status germline_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
       }
     }
     if (!retry) break;
-    if (attempt == 2) {
+    if (attempt + 1 == max_attempts) {
       free(res);
       return set_err(GQ_E_CAPACITY, "output capacity retries exhausted");
     }
