@@ -169,16 +169,25 @@ struct Pack16 {
 // (length, value) (for codes longer than the table), and the primary table (stride
 // kInfLanes) of `tb` bits indexed by the next stream bits; entries (symbol << kShift) |
 // length, 0 where the code is longer
+// An incomplete code (code words left without a symbol) is an error as it is for zlib's
+// inflate_table: kComplete (the code-length code) allows none, kOneOrNone (a block's own
+// literal/length and distance codes) a single code of length 1 or no code at all, kAny (the
+// fixed codes: 30 distance codes of 5 bits) any.
+enum : int { kComplete = 0, kOneOrNone = 1, kAny = 2 };
 template <class E, int kShift, int kTb>
-__device__ bool huff_build(const uint8_t *len, int n, Code<kTb> &c, E *tab) {
+__device__ bool huff_build(const uint8_t *len, int n, Code<kTb> &c, E *tab, int incomplete) {
   constexpr int tb = kTb;
   Pack16 cnt;
   for (int s = 0; s < n; ++s) cnt.add(len[s], 1);
-  int left = 1;
+  int left = 1, used = 0;
   for (int l = 1; l < 16; ++l) {
     left = (left << 1) - (int)cnt.get(l);
     if (left < 0) return false;  // over-subscribed
+    used += (int)cnt.get(l);
   }
+  if (left > 0 && incomplete != kAny &&
+      (incomplete == kComplete || !(used == 0 || (used == 1 && cnt.get(1) == 1))))
+    return false;  // incomplete
   Pack16 next, offs;  // next canonical code / next symbol slot per length
   int code = 0, idx = 0;
 #pragma unroll
@@ -265,9 +274,9 @@ __device__ int inflate_one(const uint8_t *comp, int64_t comp_len, const BgzfBloc
     if (type == 3) return E_INFLATE;
     if (type == 1) {  // fixed codes
       for (int s = 0; s < 288; ++s) lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-      huff_build<uint16_t, 4, kLitBits>(lens, 288, lc, lt);
+      huff_build<uint16_t, 4, kLitBits>(lens, 288, lc, lt, kAny);
       for (int s = 0; s < 30; ++s) lens[s] = 5;
-      huff_build<uint8_t, 3, kDistBits>(lens, 30, dc, dt);
+      huff_build<uint8_t, 3, kDistBits>(lens, 30, dc, dt, kAny);
     } else {  // dynamic codes
       const int hlit = (int)in.get(5) + 257, hdist = (int)in.get(5) + 1, hclen = (int)in.get(4) + 4;
       if (hlit > 286 || hdist > 30) return E_INFLATE;
@@ -277,7 +286,7 @@ __device__ int inflate_one(const uint8_t *comp, int64_t comp_len, const BgzfBloc
       for (int k = 0; k < 19; ++k) cl[k] = 0;
       for (int k = 0; k < hclen; ++k) cl[(k < 12 ? ordA >> (5 * k) : ordB >> (5 * (k - 12))) & 31] = (uint8_t)in.get(3);
       // the code-length code (lengths <= 7) in the distance table's place
-      if (!huff_build<uint8_t, 3, kDistBits>(cl, 19, dc, dt)) return E_INFLATE;
+      if (!huff_build<uint8_t, 3, kDistBits>(cl, 19, dc, dt, kComplete)) return E_INFLATE;
       int i = 0;
       while (i < hlit + hdist) {
         const int s = huff_decode<uint8_t, 3, kDistBits>(in, dt, dc);
@@ -301,8 +310,8 @@ __device__ int inflate_one(const uint8_t *comp, int64_t comp_len, const BgzfBloc
         for (int k = 0; k < rep; ++k) lens[i++] = v;
       }
       if (lens[256] == 0) return E_INFLATE;
-      if (!huff_build<uint16_t, 4, kLitBits>(lens, hlit, lc, lt)) return E_INFLATE;
-      if (!huff_build<uint8_t, 3, kDistBits>(lens + hlit, hdist, dc, dt)) return E_INFLATE;
+      if (!huff_build<uint16_t, 4, kLitBits>(lens, hlit, lc, lt, kOneOrNone)) return E_INFLATE;
+      if (!huff_build<uint8_t, 3, kDistBits>(lens + hlit, hdist, dc, dt, kOneOrNone)) return E_INFLATE;
     }
     for (;;) {  // symbols
       int sym = huff_decode<uint16_t, 4, kLitBits>(in, lt, lc);

@@ -72,6 +72,37 @@ def bgzf(data, block=65280, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, offsets=N
     return b"".join(out)
 
 
+EOF_BLOCK = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, 27) + b"\x03\x00" + bytes(8)
+
+
+def bgzf_blocks(pairs, extras=None, eof=True, offsets=None):
+    """BGZF blocks from (raw deflate payload, chunk) pairs: CRC32 and ISIZE are the chunk's,
+    whatever the payload decodes to, and the chunks are the caller's cut of the stream.
+    extras: per block (or one for all) a pair of byte strings of other gzip extra subfields
+    written before and after BC.  eof: append the empty EOF block.  offsets: a list that
+    receives each payload's file offset."""
+    out, at = [], 0
+    for k, (payload, chunk) in enumerate(pairs):
+        before, after = (extras[k] if isinstance(extras, list) else extras) if extras else (b"", b"")
+        xlen = len(before) + 6 + len(after)
+        bsize = 12 + xlen + len(payload) + 8
+        assert bsize <= 65536, "BGZF block of %d bytes" % bsize
+        out.append(struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, xlen) + before +
+                   struct.pack("<BBHH", 66, 67, 2, bsize - 1) + after + payload +
+                   struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+        if offsets is not None:
+            offsets.append(at + 12 + xlen)
+        at += bsize
+    if eof:
+        out.append(EOF_BLOCK)
+    return b"".join(out)
+
+
+def subfield(si1, si2, data):
+    """One gzip extra subfield (RFC 1952 2.3.1.1)."""
+    return struct.pack("<BBH", si1, si2, len(data)) + data
+
+
 def reg2bin(beg, end):
     """SAM specification §5.3: the smallest bin holding [beg, end)."""
     end -= 1

@@ -289,3 +289,50 @@ def test_zlib_backend_matches(tmp_path):
         e = dict(os.environ, **env)
         outs.append(subprocess.check_output([sys.executable, "-c", code], env=e).strip())
     assert outs[0] == outs[1]
+
+
+# ---- record boundaries the written BAMs above do not reach (builders: test_gpu_bamdev_streams) ----
+def test_false_sync_at_a_segment_start_is_rehopped(tmp_path):
+    """A stream just over 2 MiB past the first record is cut into exactly two boundary segments
+    (min(4 * threads, bytes >> 20)); the second starts inside a B:C array that holds nine chained
+    plausible records, so its sync is false and the segment is hopped again from the true chain."""
+    from tests import test_gpu_bamdev_streams as st
+    rng = random.Random(41)
+    recs = st._sorted(_records(rng, 12000, CONTIGS))
+    arr = b"\xEE" * 1500 + st.FAKE * 9 + b"\x01" * 16
+    hdr = bw.header(HEADER, CONTIGS)
+    r0, k, total = len(hdr), 0, 0
+    while total < (1 << 20) + 50_000:
+        total += len(recs[k])
+        k += 1
+    ref, pos = st.struct.unpack_from("<ii", recs[k], 4)
+    carrier = bw.record(ref, pos, "carrier", "4M", "ACGT", [30] * 4, tags=bw.tag_z("MD", "4") + bw.tag_b("ZF", "C", arr))
+    arr_at = r0 + total + len(carrier) - len(arr)
+    j, after = k, 0
+    while True:  # records after it until the second segment starts in the array's filler
+        n = r0 + total + len(carrier) + after
+        mid = r0 + (n - r0 + 1) // 2
+        if mid >= arr_at:
+            break
+        after += len(recs[j])
+        j += 1
+    assert arr_at <= mid <= arr_at + 1500 and 2 << 20 <= n - r0 < 3 << 20
+    data = hdr + b"".join(recs[:k]) + carrier + b"".join(recs[k:j])
+    assert len(data) == n
+    true = st.walk(data, r0)
+    first = next(o for o in range(mid, mid + 2000) if st.syncs(data, o, len(CONTIGS)))
+    assert first == arr_at + 1500 and first not in true
+    p = str(tmp_path / "f.bam")
+    with open(p, "wb") as fh:
+        fh.write(bw.bgzf(data))
+    a = load_reads(p)
+    same(a, _load_bam_py(p, InputFilters()))
+    assert a.n > 8000
+
+
+def test_record_boundary_cases_native_equals_python(tmp_path):
+    from tests import test_gpu_bamdev_streams as st
+    for name in st.BOUNDARY:
+        p = str(tmp_path / (name + ".bam"))
+        st.boundary_file(name, p)
+        same(load_reads(p), _load_bam_py(p, InputFilters()))
