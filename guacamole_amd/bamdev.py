@@ -240,10 +240,19 @@ def bai_path(path: str) -> Optional[str]:
 
 def load_reads_device(ctx: native.Context, path: str, filters: InputFilters = InputFilters(),
                       mapped: Optional[MappedBam] = None, region=None,
-                      halo: int = DEFAULT_HALO) -> Optional[DeviceReadSet]:
+                      halo: int = DEFAULT_HALO, reference=None, recompute_md: bool = False,
+                      dref=None) -> Optional[DeviceReadSet]:
     """BAM -> resident read set on ctx's GPU (None: the host loader must run, see the module
     docstring).  Raises ReadLoadError / soa.MdParseError as the host loader does.  `mapped`:
     the file already mapped (map_bams), else it is mapped here.
+
+    reference (a reference.ReferenceGenome): as the host loader's `reference=` (Read.scala:
+    223-247): reads without an MD tag are kept by the scan, and they, or every read with
+    `recompute_md`, get their MD events from the reference on the device
+    (Context.rebuild_md; timings["md_rebuild"]).  `dref`: that reference already resident
+    (Context.upload_reference of reference.for_contigs over this BAM's contig list), else it is
+    uploaded here for the rebuild.  `recompute_md` without a reference is the host loader's
+    ValueError.
 
     region (a LociSet, the multi-GPU ingest): keep only the reads overlapping it, reading only
     the BGZF blocks whose records can overlap it (gq_bam_dev_plan: from the BAI's linear index
@@ -251,9 +260,12 @@ def load_reads_device(ctx: native.Context, path: str, filters: InputFilters = In
     those of the filters within the region (the region lies inside the filters' loci).  Without
     an index the load checks the longest reference span it saw against the halo and, if a read
     could reach further back, plans again with twice that span (timings["replans"])."""
+    if recompute_md and reference is None:
+        raise ValueError("To recompute MD tags, a reference genome fasta must be provided.")
     replans = 0
     while True:
-        rs = _load_reads_device(ctx, path, filters, mapped, region, halo)
+        rs = _load_reads_device(ctx, path, filters, mapped, region, halo, reference=reference,
+                                recompute_md=recompute_md, dref=dref)
         if rs is None or region is None or rs.timings.get("plan") is None:
             break
         plan = rs.timings["plan"]
@@ -267,7 +279,28 @@ def load_reads_device(ctx: native.Context, path: str, filters: InputFilters = In
     return rs
 
 
-def _load_reads_device(ctx, path, filters, mapped, region, halo, use_plan=True):
+def _rebuild_md(ctx, dr, n, names, filters, reference, recompute_md, dref) -> Dict[str, object]:
+    """The load's MD rebuild (load_reads_device's `reference`).  Afterwards no read lacks events,
+    so the host path's has_md_tag subset (reads.load_reads) is empty and nothing is compacted:
+    counted on the device, not assumed."""
+    own = dref is None
+    if own:
+        dref = ctx.upload_reference(reference.for_contigs(names))
+    try:
+        t = time.perf_counter()
+        out = ctx.rebuild_md(dr, dref, recompute_md)
+        missing = ctx.missing_md(dr) if filters.has_md_tag else 0  # (counted on the device: one word comes back)
+        out["wall_s"] = time.perf_counter() - t
+    finally:
+        if own:
+            dref.free()
+    if missing:
+        raise AssertionError("%d reads lack MD events after the rebuild from the reference" % missing)
+    return out
+
+
+def _load_reads_device(ctx, path, filters, mapped, region, halo, use_plan=True, reference=None, recompute_md=False,
+                       dref=None):
     L = native.lib()
     planned = region is not None and use_plan
     m = mapped if mapped is not None and (mapped.h or not mapped.ok) else MappedBam(path, populate=not planned)
@@ -296,7 +329,8 @@ def _load_reads_device(ctx, path, filters, mapped, region, halo, use_plan=True):
             L.gq_bam_dev_close(h)
             return None
         f = gq_bam_dev_filters(int(filters.non_duplicate), int(filters.passed_vendor_quality_checks),
-                               int(filters.is_paired), int(filters.has_md_tag), 0, None, None, None, len(rg_ids),
+                               int(filters.is_paired), int(filters.has_md_tag and reference is None), 0, None, None,
+                               None, len(rg_ids),
                                b"".join(x.encode() + b"\0" for x in rg_ids) or None)
         keep = []
         loci = region
@@ -311,7 +345,8 @@ def _load_reads_device(ctx, path, filters, mapped, region, halo, use_plan=True):
         rc = L.gq_bam_dev_scan(h, C.byref(f), first.ctypes.data, C.byref(z))
         if rc == GQ_E_PLAN:  # a record runs past a planned segment: read the whole file
             L.gq_bam_dev_close(h)
-            return _load_reads_device(ctx, path, filters, None, region, halo, use_plan=False)
+            return _load_reads_device(ctx, path, filters, None, region, halo, use_plan=False, reference=reference,
+                                      recompute_md=recompute_md, dref=dref)
         if rc == GQ_E_HIP:
             L.gq_bam_dev_close(h)
             return None
@@ -343,6 +378,12 @@ def _load_reads_device(ctx, path, filters, mapped, region, halo, use_plan=True):
     t4 = time.perf_counter()
     dr = native.DeviceReads(ctx, out, None)
     timings = {k: float(getattr(z, k)) for k in ("map_ms", "h2d_ms", "inflate_ms", "records_ms", "parse_ms")}
+    if reference is not None:
+        try:
+            timings["md_rebuild"] = _rebuild_md(ctx, dr, int(z.n_reads), names, filters, reference, recompute_md, dref)
+        except BaseException:
+            L.gq_bam_dev_close(h)
+            raise
     info = ctx.proj_stats(dr)
     timings.update(fill_ms=float(fill_ms.value), derive_ms=float(info.get("derive_ms", 0.0)),
                    open_s=t1 - t0, scan_s=t2 - t1, total_s=time.perf_counter() - t0,

@@ -114,19 +114,22 @@ def germline_threshold_reads(ctx: native.Context, rs: ReadSet, loci, threshold: 
 
 
 def somatic_standard_reads(ctx: native.Context, tumor: ReadSet, normal: ReadSet, loci, _gather=None,
-                           reference=None, _stats=None, **params) -> Optional[List[dict]]:
+                           reference=None, _stats=None, _dref=None, **params) -> Optional[List[dict]]:
     """pileupFlatMapTwoRDDs(tumor, normal, partitions, skipEmpty=true, findPotentialVariantAtLocus,
     referenceGenome) + the driver's filters on the GPU.  Rows as the oracle's somatic_standard
     (contig by name).  reference: a reference.ReferenceGenome (--reference-fasta) or None.
-    _gather: the gather device of a multi-GPU run (rank 0 gets every rank's rows, others None)."""
+    _gather: the gather device of a multi-GPU run (rank 0 gets every rank's rows, others None).
+    _dref: that reference already resident for the read sets' contig list (the caller frees it);
+    else it is uploaded for the call."""
     if tumor.contig_names != normal.contig_names:
         raise ValueError("tumor and normal reads must share the contig list")
-    dref = None if reference is None else ctx.upload_reference(reference.for_contigs(tumor.contig_names))
+    own = reference is not None and _dref is None
+    dref = ctx.upload_reference(reference.for_contigs(tumor.contig_names)) if own else _dref
     try:
         calls = ctx.somatic_standard(device_reads(ctx, tumor), device_reads(ctx, normal), loci, reference=dref,
                                      **params)
     finally:
-        if dref is not None:
+        if own:
             dref.free()
     if _stats is not None:
         _stats["visited_loci"] = int(calls.visited_loci)
@@ -275,37 +278,50 @@ def parquet_options(args, flat=None, contig_index=None, rows_contig=None, rows_p
 
 def device_ingest(args, *paths: str) -> bool:
     """Decode these BAMs on the GPU (bamdev.load_reads_device) rather than with the host
-    loader: BAM input without MD recomputation or contig lengths from the reads (GQ_INGEST=host
-    forces the host loader).  Under torch.distributed.run each rank decodes only the part of the
-    file its tasks need (distributed.device_ingest_ranks)."""
+    loader: BAM input with contig lengths from the sequence dictionary (GQ_INGEST=host forces
+    the host loader).  With --reference-fasta the device load rebuilds MD events from the
+    resident reference (Context.rebuild_md), for the reads without a tag or, with
+    --recompute-md-tags, for every read; --recompute-md-tags without a FASTA stays with the
+    host loader, which refuses it.  Under torch.distributed.run each rank decodes only the part
+    of the file its tasks need (distributed.device_ingest_ranks); multi-rank runs with a
+    reference keep the host loader (a device ingest with a reference across ranks is not
+    built)."""
     import os
     if os.environ.get("GQ_INGEST", "device") == "host":
         return False
-    if getattr(args, "recompute_md_tags", False) or getattr(args, "no_sequence_dictionary", False):
+    if getattr(args, "no_sequence_dictionary", False):
         return False
-    if getattr(args, "reference_fasta", ""):
+    has_ref = bool(getattr(args, "reference_fasta", ""))
+    if getattr(args, "recompute_md_tags", False) and not has_ref:
         return False
+    if has_ref:
+        from .distributed import rank_info
+        if rank_info()[1] > 1:
+            return False
     return all(is_bam(p) for p in paths)
 
 
-def load_pair_device(ctx, ctx2, paths, filters, mapped):
+def load_pair_device(ctx, ctx2, paths, filters, mapped, reference=None, recompute_md=False, drefs=(None, None)):
     """Two BAMs decoded on the device at once: the second on ctx2 (its own stream) on a host
     thread while the first loads on ctx, so one's copy overlaps the other's inflate (ctypes
     releases the GIL).  The second read set is then registered with ctx (device pointers are
-    valid across contexts of one device) and keeps ctx2 alive."""
+    valid across contexts of one device) and keeps ctx2 alive.  reference / recompute_md /
+    drefs (each file's resident reference, or None): load_reads_device's."""
     import threading
     import weakref
     box = {}
 
     def second():
         try:
-            box["rs"] = load_reads_device(ctx2, paths[1], filters, mapped[paths[1]])
+            box["rs"] = load_reads_device(ctx2, paths[1], filters, mapped[paths[1]], reference=reference,
+                                          recompute_md=recompute_md, dref=drefs[1])
         except BaseException as e:  # re-raised below
             box["err"] = e
     th = threading.Thread(target=second)
     th.start()
     try:
-        first = load_reads_device(ctx, paths[0], filters, mapped[paths[0]])
+        first = load_reads_device(ctx, paths[0], filters, mapped[paths[0]], reference=reference,
+                                  recompute_md=recompute_md, dref=drefs[0])
     finally:
         th.join()
     if "err" in box:
@@ -315,6 +331,61 @@ def load_pair_device(ctx, ctx2, paths, filters, mapped):
         rs._device[id(ctx)] = (weakref.ref(ctx), rs.reads)
         rs._ctx2 = ctx2
     return [first, rs]
+
+
+def resident_references(ctx, reference, mapped, paths):
+    """The reference resident once for BAMs that share a contig list: per path the handle
+    (Context.upload_reference over that file's header contigs) or None where the file is not
+    mapped for the device load; files with equal contig lists share one handle.  Returns
+    (handles per path, [(contig names, handle)])."""
+    made = []
+    out = []
+    for path in paths:
+        m = mapped.get(path)
+        if reference is None or m is None or not m.ok or not m.h:
+            out.append(None)
+            continue
+        names = m.contigs()[0]
+        hit = next((h for nm, h in made if nm == names), None)
+        if hit is None:
+            hit = ctx.upload_reference(reference.for_contigs(names))
+            made.append((names, hit))
+        out.append(hit)
+    return out, made
+
+
+def load_product_reads(args, filters, *paths):
+    """The load block the CSV products share (allele-evidence, genotype-likelihoods,
+    pileup-elements, pileup-counts, somatic-likelihoods): the device ingest where it applies
+    (two files: load_pair_device), else the host loader.  --reference-fasta supplies MD tags by
+    Read.fromSAMRecord's rule (reads without one, or every read with --recompute-md-tags) in
+    both loaders; the pileups' reference base stays the MD-derived one.  Returns (the context or
+    None if none was opened, the read sets)."""
+    reference = None
+    if getattr(args, "reference_fasta", ""):
+        from .reference import ReferenceGenome
+        reference = ReferenceGenome.load_fasta(args.reference_fasta)
+    ctx = None
+    sets = [None] * len(paths)
+    if device_ingest(args, *paths):
+        maps = map_bams(list(paths))  # the files mapped on a host thread while the context starts
+        ctx = native.Context(args.device)
+        ctx2 = native.Context(args.device) if len(paths) == 2 else None  # (the second load's own stream)
+        mapped = maps["join"]()
+        drefs, made = resident_references(ctx, reference, mapped, paths)
+        try:
+            if len(paths) == 2:
+                sets = load_pair_device(ctx, ctx2, list(paths), filters, mapped, reference, args.recompute_md_tags,
+                                        drefs)
+            else:
+                sets = [load_reads_device(ctx, paths[0], filters, mapped[paths[0]], reference=reference,
+                                          recompute_md=args.recompute_md_tags, dref=drefs[0])]
+        finally:
+            for _, h in made:
+                h.free()
+    sets = [s if s is not None else load_reads(path, filters, reference=reference, recompute_md=args.recompute_md_tags)
+            for s, path in zip(sets, paths)]
+    return ctx, sets
 
 
 def germline_threshold_main(argv: Sequence[str]) -> int:
@@ -454,59 +525,68 @@ def somatic_standard_main(argv: Sequence[str]) -> int:
         reference = ReferenceGenome.load_fasta(args.reference_fasta)
     ctx = None
     sets = [None, None]
+    made = []  # [(contig names, resident reference)] of the device loads
     mine = None  # this rank's loci ranges, when the device ingest planned them
-    if device_ingest(args, args.tumor_reads, args.normal_reads):
-        if world == 1:
-            maps = map_bams([args.tumor_reads, args.normal_reads])
-            t = clock.t()
-            ctx = native.Context(args.device)
-            ctx2 = native.Context(args.device)  # the normal's load: its own stream, alongside the tumor's
-            clock.note("ctx_open_s", clock.t() - t)
-            mapped = maps["join"]()
-            sets = load_pair_device(ctx, ctx2, [args.tumor_reads, args.normal_reads], f, mapped)
-        else:
-            ctx = native.Context(local)
-            got = device_ingest_ranks(ctx, [args.tumor_reads, args.normal_reads], f, builder, args.parallelism,
-                                      args.partition_accuracy, rank, world, gdev)
-            if got is not None:
-                sets, mine, _ = got
-    tumor, normal = [s if s is not None else
-                     load_reads(path, f, reference=reference, recompute_md=args.recompute_md_tags,
-                                contig_lengths_from_dictionary=not args.no_sequence_dictionary)
-                     for s, path in zip(sets, (args.tumor_reads, args.normal_reads))]
-    if tumor.contig_lengths_map != normal.contig_lengths_map:
-        raise ValueError("Tumor and normal samples have different sequence dictionaries.")
-    clock.mark("load_reads")
-    loci = builder.result(normal.contig_lengths_map)
-    if mine is None:
-        parts = partition(loci, args.parallelism, args.partition_accuracy, tumor, normal, world=world)
-        flat = flatten_partitions(parts, tumor.contig_index())
-    else:
-        flat = mine
-    if ctx is None:
-        ctx = native.Context(local if world > 1 else args.device)
-    sample = tumor.sample_names[0] if tumor.sample_names else "default"
-    if world > 1:
+    try:  # (the resident references are freed whatever the loads or the call raise)
+        if device_ingest(args, args.tumor_reads, args.normal_reads):
+            if world == 1:
+                maps = map_bams([args.tumor_reads, args.normal_reads])
+                t = clock.t()
+                ctx = native.Context(args.device)
+                ctx2 = native.Context(args.device)  # the normal's load: its own stream, alongside the tumor's
+                clock.note("ctx_open_s", clock.t() - t)
+                mapped = maps["join"]()
+                # the reference goes to HBM once: the loads rebuild MD events from it, the call reads it
+                drefs, made = resident_references(ctx, reference, mapped, [args.tumor_reads, args.normal_reads])
+                sets = load_pair_device(ctx, ctx2, [args.tumor_reads, args.normal_reads], f, mapped, reference,
+                                        args.recompute_md_tags, drefs)
+            else:
+                ctx = native.Context(local)
+                got = device_ingest_ranks(ctx, [args.tumor_reads, args.normal_reads], f, builder, args.parallelism,
+                                          args.partition_accuracy, rank, world, gdev)
+                if got is not None:
+                    sets, mine, _ = got
+        tumor, normal = [s if s is not None else
+                         load_reads(path, f, reference=reference, recompute_md=args.recompute_md_tags,
+                                    contig_lengths_from_dictionary=not args.no_sequence_dictionary)
+                         for s, path in zip(sets, (args.tumor_reads, args.normal_reads))]
+        if tumor.contig_lengths_map != normal.contig_lengths_map:
+            raise ValueError("Tumor and normal samples have different sequence dictionaries.")
+        clock.mark("load_reads")
+        loci = builder.result(normal.contig_lengths_map)
         if mine is None:
-            rr = assign_tasks_to_ranks(flat, world, [tumor, normal], len(tumor.contig_names))
-            tumor, flat = rank_share(tumor, flat, rr, rank)
-            normal = normal.subset(reads_overlapping(normal, *flat[:3]))
-        else:  # each rank read its own part: the first tumor sample of the lowest rank that has one
-            sample = next((n[0] for n in all_gather_objects(list(tumor.sample_names)) if n), "default")
-    stats: Dict[str, int] = {}
-    all_flat = None
-    if output_kind(args.out) == "parquet":  # every rank's tasks: the part file of each record
-        all_flat = _all_flat(flat) if world > 1 else flat
-    rows = somatic_standard_reads(
-        ctx, tumor, normal, flat, odds=args.odds, min_mapq=args.min_mapq,
-        filter_multi_allelic=int(args.filter_multi_allelic), max_read_depth=args.max_tumor_read_depth,
-        min_tumor_read_depth=args.min_tumor_read_depth, max_tumor_read_depth=args.max_tumor_read_depth,
-        min_normal_read_depth=args.min_normal_read_depth,
-        min_tumor_alternate_read_depth=args.min_tumor_alternate_read_depth, min_lod=args.min_lod,
-        min_likelihood=args.min_likelihood, min_vaf=args.min_vaf,
-        min_average_mapping_quality=args.min_average_mapping_quality,
-        min_average_base_quality=args.min_average_base_quality, max_median_mismatches=args.max_median_mismatches,
-        apply_filters=1, _gather=gdev if world > 1 else None, reference=reference, _stats=stats)
+            parts = partition(loci, args.parallelism, args.partition_accuracy, tumor, normal, world=world)
+            flat = flatten_partitions(parts, tumor.contig_index())
+        else:
+            flat = mine
+        if ctx is None:
+            ctx = native.Context(local if world > 1 else args.device)
+        sample = tumor.sample_names[0] if tumor.sample_names else "default"
+        if world > 1:
+            if mine is None:
+                rr = assign_tasks_to_ranks(flat, world, [tumor, normal], len(tumor.contig_names))
+                tumor, flat = rank_share(tumor, flat, rr, rank)
+                normal = normal.subset(reads_overlapping(normal, *flat[:3]))
+            else:  # each rank read its own part: the first tumor sample of the lowest rank that has one
+                sample = next((n[0] for n in all_gather_objects(list(tumor.sample_names)) if n), "default")
+        stats: Dict[str, int] = {}
+        all_flat = None
+        if output_kind(args.out) == "parquet":  # every rank's tasks: the part file of each record
+            all_flat = _all_flat(flat) if world > 1 else flat
+        rows = somatic_standard_reads(
+            ctx, tumor, normal, flat, odds=args.odds, min_mapq=args.min_mapq,
+            filter_multi_allelic=int(args.filter_multi_allelic), max_read_depth=args.max_tumor_read_depth,
+            min_tumor_read_depth=args.min_tumor_read_depth, max_tumor_read_depth=args.max_tumor_read_depth,
+            min_normal_read_depth=args.min_normal_read_depth,
+            min_tumor_alternate_read_depth=args.min_tumor_alternate_read_depth, min_lod=args.min_lod,
+            min_likelihood=args.min_likelihood, min_vaf=args.min_vaf,
+            min_average_mapping_quality=args.min_average_mapping_quality,
+            min_average_base_quality=args.min_average_base_quality, max_median_mismatches=args.max_median_mismatches,
+            apply_filters=1, _gather=gdev if world > 1 else None, reference=reference, _stats=stats,
+            _dref=next((h for nm, h in made if nm == tumor.contig_names), None))
+    finally:
+        for _, h in made:
+            h.free()
     clock.mark("call")
     report = dict(rank=rank, reads=[int(tumor.n), int(normal.n)], ingest="device" if isinstance(tumor, DeviceReadSet)
                   else "host", device_ingest=[getattr(x, "timings", None) for x in (tumor, normal)], **stats)
@@ -775,6 +855,9 @@ def allele_evidence_main(argv: Sequence[str]) -> int:
     p.add_argument("--partition-accuracy", type=int, default=250,
                    help="Num micro partitions per task in loci partitioning; 0 = uniform")
     p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     args = p.parse_args(argv)
     single_process_only("allele-evidence")
@@ -782,14 +865,7 @@ def allele_evidence_main(argv: Sequence[str]) -> int:
         raise FileExistsError("Output path %s already exists" % args.out)
     builder = _loci_builder(args)
     filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
-    ctx = None
-    rs = None
-    if device_ingest(args, args.reads):
-        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
-        ctx = native.Context(args.device)
-        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
-    if rs is None:
-        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    ctx, (rs,) = load_product_reads(args, filters, args.reads)
     loci = builder.result(rs.contig_lengths_map)
     parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
     flat = flatten_partitions(parts, rs.contig_index())
@@ -866,6 +942,9 @@ def genotype_likelihoods_main(argv: Sequence[str]) -> int:
     p.add_argument("--partition-accuracy", type=int, default=250,
                    help="Num micro partitions per task in loci partitioning; 0 = uniform")
     p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     args = p.parse_args(argv)
     single_process_only("genotype-likelihoods")
@@ -873,14 +952,7 @@ def genotype_likelihoods_main(argv: Sequence[str]) -> int:
         raise FileExistsError("Output path %s already exists" % args.out)
     builder = _loci_builder(args)
     filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
-    ctx = None
-    rs = None
-    if device_ingest(args, args.reads):
-        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
-        ctx = native.Context(args.device)
-        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
-    if rs is None:
-        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    ctx, (rs,) = load_product_reads(args, filters, args.reads)
     loci = builder.result(rs.contig_lengths_map)
     parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
     flat = flatten_partitions(parts, rs.contig_index())
@@ -948,6 +1020,9 @@ def pileup_elements_main(argv: Sequence[str]) -> int:
     p.add_argument("--partition-accuracy", type=int, default=250,
                    help="Num micro partitions per task in loci partitioning; 0 = uniform")
     p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     args = p.parse_args(argv)
     single_process_only("pileup-elements")
@@ -955,14 +1030,7 @@ def pileup_elements_main(argv: Sequence[str]) -> int:
         raise FileExistsError("Output path %s already exists" % args.out)
     builder = _loci_builder(args)
     filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
-    ctx = None
-    rs = None
-    if device_ingest(args, args.reads):
-        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
-        ctx = native.Context(args.device)
-        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
-    if rs is None:
-        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    ctx, (rs,) = load_product_reads(args, filters, args.reads)
     loci = builder.result(rs.contig_lengths_map)
     parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
     flat = flatten_partitions(parts, rs.contig_index())
@@ -1046,6 +1114,9 @@ def somatic_likelihoods_main(argv: Sequence[str]) -> int:
     p.add_argument("--partition-accuracy", type=int, default=250,
                    help="Num micro partitions per task in loci partitioning; 0 = uniform")
     p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     args = p.parse_args(argv)
     single_process_only("somatic-likelihoods")
@@ -1054,15 +1125,7 @@ def somatic_likelihoods_main(argv: Sequence[str]) -> int:
     builder = _loci_builder(args)
     f = InputFilters.make(overlaps_loci=builder, non_duplicate=True, passed_vendor_quality_checks=True,
                           has_md_tag=True)
-    ctx = None
-    sets = [None, None]
-    if device_ingest(args, args.tumor_reads, args.normal_reads):
-        maps = map_bams([args.tumor_reads, args.normal_reads])
-        ctx = native.Context(args.device)
-        ctx2 = native.Context(args.device)  # the normal's load: its own stream, alongside the tumor's
-        sets = load_pair_device(ctx, ctx2, [args.tumor_reads, args.normal_reads], f, maps["join"]())
-    tumor, normal = [s if s is not None else load_reads(path, f, recompute_md=args.recompute_md_tags)
-                     for s, path in zip(sets, (args.tumor_reads, args.normal_reads))]
+    ctx, (tumor, normal) = load_product_reads(args, f, args.tumor_reads, args.normal_reads)
     if tumor.contig_lengths_map != normal.contig_lengths_map:
         raise ValueError("Tumor and normal samples have different sequence dictionaries.")
     loci = builder.result(normal.contig_lengths_map)
@@ -1161,6 +1224,9 @@ def pileup_counts_main(argv: Sequence[str]) -> int:
     p.add_argument("--partition-accuracy", type=int, default=250,
                    help="Num micro partitions per task in loci partitioning; 0 = uniform")
     p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     p.add_argument("--chunk-loci", type=int, default=1 << 24,
                    help="Loci per library call (whole tasks; a larger task goes alone)")
@@ -1172,14 +1238,7 @@ def pileup_counts_main(argv: Sequence[str]) -> int:
         raise ValueError("--chunk-loci must be at least 1")
     builder = _loci_builder(args)
     filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
-    ctx = None
-    rs = None
-    if device_ingest(args, args.reads):
-        maps = map_bams([args.reads])  # the file mapped on a host thread while the context starts
-        ctx = native.Context(args.device)
-        rs = load_reads_device(ctx, args.reads, filters, maps["join"]()[args.reads])
-    if rs is None:
-        rs = load_reads(args.reads, filters, recompute_md=args.recompute_md_tags)
+    ctx, (rs,) = load_product_reads(args, filters, args.reads)
     loci = builder.result(rs.contig_lengths_map)
     parts = partition(loci, args.parallelism, args.partition_accuracy, rs)
     flat = flatten_partitions(parts, rs.contig_index())

@@ -1032,6 +1032,7 @@ struct gq_ctx {
     stage_cv.wait(lk, [this] { return stage_ready; });
     return stage_err;
   }
+  float md_spans[3] = {0, 0, 0};                   // the last gq_reads_rebuild_md: count, scan, fill (ms)
   void *pin = nullptr;                             // pinned host staging for the small per-call copies
   size_t pin_n = 0;
   hipError_t pinned(size_t bytes) {                // pin has >= bytes (contents not kept)
@@ -1129,6 +1130,19 @@ struct gq_dev_reads {
   mutable void *mproj = nullptr;  // somatic margin projection (a biased byte per locus-read), for mproj_mapq
   mutable int mproj_mapq = -1;
   mutable void *mnb = nullptr;    // per slice: 1 if a margin term there is kMargin8None (no bound)
+};
+
+// A reference genome resident in HBM (ReferenceBroadcast.scala:39-55): the contigs of a read
+// set's contig list, each at a 512-aligned offset and padded with 'N' to a whole 512-locus block
+// past its end (somatic_proj reads 8 bases per lane of an aligned block; md_rebuild reads 8 bases
+// at a contig's last one).
+struct gq_reference {
+  int device = 0;
+  int32_t n_contigs = 0;
+  void *bytes = nullptr;
+  int64_t *d_off = nullptr;
+  int64_t *d_len = nullptr;       // the contigs' lengths beside d_off (-1 where absent), same allocation
+  std::vector<int64_t> off, len;  // host copies; off = -1 for a contig the reference lacks
 };
 
 namespace gq {

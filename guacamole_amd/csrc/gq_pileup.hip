@@ -1902,6 +1902,8 @@ __global__ __launch_bounds__(kBlock) void calls_image(const CallRec *__restrict_
 
 }  // namespace
 
+#include "gq_md_rebuild.h"  // md_rebuild_count / md_rebuild_fill (gq_reads_rebuild_md)
+
 // ==========================================================================================
 // Host side: context, resident read sets, entry points
 // ==========================================================================================
@@ -2435,6 +2437,174 @@ gq_status gq_reads_rederive(gq_ctx *c, gq_dev_reads *d) {
   const gq_status st = derive_shape_impl(c, d, R.md_len, true);
   d->derive_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
   return st;
+}
+
+gq_status gq_reads_rebuild_md(gq_ctx *c, gq_dev_reads *d, const gq_reference *ref, int32_t recompute_all,
+                              gq_md_rebuild_info *info) {
+  if (!c || !d || !ref) return set_err(GQ_E_ARG, "gq_reads_rebuild_md: null argument");
+  if (d->ctx != c) return set_err(GQ_E_ARG, "gq_reads_rebuild_md: the read set belongs to another context");
+  if (ref->n_contigs != d->d.n_contigs)
+    return set_err(GQ_E_ARG, "reference covers %d contigs, the read set %d", ref->n_contigs, d->d.n_contigs);
+  if (ref->device != c->device) return set_err(GQ_E_ARG, "reference uploaded to another device");
+  gq_md_rebuild_info inf{};
+  inf.read = -1;
+  inf.md_events = d->d.md_len;
+  if (info) *info = inf;
+  c->md_spans[0] = c->md_spans[1] = c->md_spans[2] = 0;  // (a call that rebuilds nothing, or fails, has none)
+  HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(d);
+    if (vs) return vs;
+  }
+  const int64_t n = d->d.n_reads;
+  if (n == 0) return GQ_OK;
+  // temporaries and the new per-read arrays; freed on every path that does not install them
+  struct Bufs {
+    std::vector<void *> p;
+    ~Bufs() {
+      for (void *x : p) (void)hipFree(x);
+    }
+    hipError_t get(void **out, size_t bytes) {
+      *out = nullptr;
+      const hipError_t e = hipMalloc(out, std::max(bytes, (size_t)16));
+      if (e == hipSuccess) p.push_back(*out);
+      return e;
+    }
+    void keep(void *x) { p.erase(std::find(p.begin(), p.end(), x)); }
+  } bufs;
+  struct Events {
+    hipEvent_t e[4] = {};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
+  void *q;
+  HIP_TRY(bufs.get(&q, sizeof(int64_t) * ((size_t)n + 1)));
+  int64_t *ev_cnt = (int64_t *)q;
+  HIP_TRY(bufs.get(&q, sizeof(int64_t) * ((size_t)n + 1)));
+  int64_t *new_off = (int64_t *)q;
+  HIP_TRY(bufs.get(&q, sizeof(int32_t) * (size_t)n));
+  int32_t *new_nmd = (int32_t *)q;
+  HIP_TRY(bufs.get(&q, sizeof(uint16_t) * (size_t)n));
+  uint16_t *new_nmm = (uint16_t *)q;
+  constexpr int kErrWords = 1 + mdr::kCountSpread;  // the error key, then the rebuilt-read counters
+  HIP_TRY(bufs.get(&q, sizeof(unsigned long long) * kErrWords));
+  unsigned long long *err = (unsigned long long *)q;
+  HIP_TRY(hipMemsetAsync(err, 0xFF, sizeof(unsigned long long), c->stream));
+  HIP_TRY(hipMemsetAsync(err + 1, 0, sizeof(unsigned long long) * mdr::kCountSpread, c->stream));
+  HIP_TRY(hipMemsetAsync(ev_cnt + n, 0, sizeof(int64_t), c->stream));
+  const mdr::RefDev rd{(const uint8_t *)ref->bytes, ref->d_off, ref->d_len};
+  const unsigned nb = (unsigned)(((int64_t)n * mdr::kLanes + kBlock - 1) / kBlock);
+  HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+  hipLaunchKernelGGL(mdr::md_rebuild_count, dim3(nb), dim3(kBlock), 0, c->stream, d->d, rd, (int)recompute_all, ev_cnt,
+                     new_nmd, new_nmm, err);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+  {
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t *)ev_cnt, new_off, (int)(n + 1), c->stream));
+    void *tmp;
+    HIP_TRY(bufs.get(&tmp, tb));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)ev_cnt, new_off, (int)(n + 1), c->stream));
+  }
+  HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+  unsigned long long herr[kErrWords] = {~0ull};
+  int64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(herr, err, sizeof(herr), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&total, new_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (herr[0] != ~0ull) {  // the read set is left as it was
+    inf.read = (int64_t)(herr[0] >> 8);
+    inf.code = (int32_t)(herr[0] & 0xFF);
+    if (info) *info = inf;
+    switch (inf.code) {
+      case mdr::kNoContig:
+        return set_err(GQ_E_ARG, "MD rebuild: read %lld lies on a contig the reference lacks", (long long)inf.read);
+      case mdr::kBadOp:
+        return set_err(GQ_E_ARG, "MD rebuild: read %lld: Cannot handle operator: N", (long long)inf.read);
+      case mdr::kPastEnd:
+        return set_err(GQ_E_ARG, "MD rebuild: read %lld: alignment runs past the end of the reference or read sequence",
+                       (long long)inf.read);
+      default:
+        return set_err(GQ_E_MD_PARSE, "MD rebuild: read %lld: a reference base no MD tag can hold", (long long)inf.read);
+    }
+  }
+  inf.rebuilt = recompute_all ? n : 0;
+  for (int k = 1; k < kErrWords && !recompute_all; ++k) inf.rebuilt += (int64_t)herr[k];
+  if (inf.rebuilt == 0) {  // every read keeps its tag: nothing changes, nothing is re-derived
+    if (info) *info = inf;
+    return GQ_OK;
+  }
+  HIP_TRY(bufs.get(&q, sizeof(uint32_t) * (size_t)std::max<int64_t>(total, 1)));
+  uint32_t *new_ev = (uint32_t *)q;
+  hipLaunchKernelGGL(mdr::md_rebuild_fill, dim3(nb), dim3(kBlock), 0, c->stream, d->d, rd, (int)recompute_all,
+                     (const int64_t *)new_off, new_ev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+  // nothing queued may still read the old arrays (nor the derived buffers: gq_reads_rederive)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->side));
+  (void)hipEventElapsedTime(&c->md_spans[0], ev.e[0], ev.e[1]);
+  (void)hipEventElapsedTime(&c->md_spans[1], ev.e[1], ev.e[2]);
+  (void)hipEventElapsedTime(&c->md_spans[2], ev.e[2], ev.e[3]);
+  inf.ms = c->md_spans[0] + c->md_spans[1] + c->md_spans[2];
+  DevReads &R = d->d;
+  // the set's own old arrays are freed; a wrapped set's belong to the caller
+  auto install = [&](const void *old, void *now) {
+    auto it = std::find(d->owned.begin(), d->owned.end(), const_cast<void *>(old));
+    if (it != d->owned.end()) {
+      (void)hipFree(*it);
+      *it = now;
+    } else {
+      d->owned.push_back(now);
+    }
+    bufs.keep(now);
+  };
+  install(R.md_off, new_off);
+  install(R.n_md, new_nmd);
+  install(R.n_mismatch, new_nmm);
+  install(R.md_ev, new_ev);
+  R.md_off = new_off;
+  R.n_md = new_nmd;
+  R.n_mismatch = new_nmm;
+  R.md_ev = new_ev;
+  R.md_len = total;
+  inf.md_events = total;
+  if (info) *info = inf;
+  return gq_reads_rederive(c, d);
+}
+
+gq_status gq_reads_missing_md(const gq_dev_reads *d, int64_t *out) {
+  if (!d || !out) return set_err(GQ_E_ARG, "gq_reads_missing_md: null argument");
+  *out = 0;
+  const int64_t n = d->d.n_reads;
+  if (n == 0) return GQ_OK;
+  gq_ctx *c = d->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = sizeof(unsigned long long) * mdr::kCountSpread;
+  void *cnt = nullptr;
+  HIP_TRY(hipMalloc(&cnt, bytes));
+  unsigned long long h[mdr::kCountSpread] = {};
+  hipError_t e = hipMemsetAsync(cnt, 0, bytes, c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mdr::md_missing_count, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       d->d.n_md, n, (unsigned long long *)cnt);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, cnt, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(cnt);
+  HIP_TRY(e);
+  for (unsigned long long x : h) *out += (int64_t)x;
+  return GQ_OK;
+}
+
+gq_status gq_md_rebuild_spans(const gq_ctx *c, float *out3) {
+  if (!c || !out3) return set_err(GQ_E_ARG, "gq_md_rebuild_spans: null argument");
+  std::copy(c->md_spans, c->md_spans + 3, out3);
+  return GQ_OK;
 }
 
 gq_status gq_reads_get_info(const gq_dev_reads *dc, gq_reads_info *out) {

@@ -1435,17 +1435,7 @@ gq_status fetch_somatic_records(gq_ctx *c, const Counters &hc, unsigned long lon
 
 }  // namespace
 
-// A reference genome resident in HBM (ReferenceBroadcast.scala:39-55): the contigs of a read
-// set's contig list, each at a 512-aligned offset and padded with 'N' to a whole 512-locus block
-// past its end (somatic_proj reads 8 bases per lane of an aligned block).
-struct gq_reference {
-  int device = 0;
-  int32_t n_contigs = 0;
-  void *bytes = nullptr;
-  int64_t *d_off = nullptr;
-  std::vector<int64_t> off, len;  // host copies; off = -1 for a contig the reference lacks
-};
-
+// (struct gq_reference: gq_host.h)
 extern "C" {
 
 gq_status gq_reference_upload(gq_ctx *c, int32_t n_contigs, const uint8_t *const *bases, const int64_t *lengths,
@@ -1470,7 +1460,7 @@ gq_status gq_reference_upload(gq_ctx *c, int32_t n_contigs, const uint8_t *const
     return st;
   };
   if (hipMalloc(&r->bytes, (size_t)std::max<int64_t>(tot, 512)) != hipSuccess ||
-      hipMalloc((void **)&r->d_off, sizeof(int64_t) * (size_t)std::max(n_contigs, 1)) != hipSuccess)
+      hipMalloc((void **)&r->d_off, sizeof(int64_t) * 2 * (size_t)std::max(n_contigs, 1)) != hipSuccess)
     return fail(set_err(GQ_E_HIP, "gq_reference_upload: hipMalloc of %lld bytes failed", (long long)tot));
   if (hipMemsetAsync(r->bytes, 'N', (size_t)std::max<int64_t>(tot, 512), c->stream) != hipSuccess)
     return fail(set_err(GQ_E_HIP, "gq_reference_upload: memset failed"));
@@ -1482,6 +1472,10 @@ gq_status gq_reference_upload(gq_ctx *c, int32_t n_contigs, const uint8_t *const
   if (n_contigs > 0 && hipMemcpyAsync(r->d_off, r->off.data(), sizeof(int64_t) * (size_t)n_contigs,
                                       hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return fail(set_err(GQ_E_HIP, "gq_reference_upload: offsets copy failed"));
+  r->d_len = r->d_off + std::max(n_contigs, 1);  // (one allocation: the lengths behind the offsets)
+  if (n_contigs > 0 && hipMemcpyAsync(r->d_len, r->len.data(), sizeof(int64_t) * (size_t)n_contigs,
+                                      hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return fail(set_err(GQ_E_HIP, "gq_reference_upload: lengths copy failed"));
   if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(set_err(GQ_E_HIP, "gq_reference_upload: sync failed"));
   *out = r;
   return GQ_OK;

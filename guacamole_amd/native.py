@@ -239,6 +239,11 @@ class gq_pileup_count_rows(C.Structure):
                 ("block_bytes", C.c_int64), ("block_", C.c_void_p)]
 
 
+class gq_md_rebuild_info(C.Structure):
+    _fields_ = [("read", C.c_int64), ("code", C.c_int32), ("pad", C.c_int32), ("rebuilt", C.c_int64),
+                ("md_events", C.c_int64), ("ms", C.c_float)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -254,7 +259,7 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
             "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements",
             "gq_somatic_likelihoods_call", "gq_free_somatic_likelihoods", "gq_pileup_counts_call",
-            "gq_free_pileup_counts")
+            "gq_free_pileup_counts", "gq_reads_rebuild_md", "gq_md_rebuild_spans", "gq_reads_missing_md")
 
 
 def lib():
@@ -269,7 +274,7 @@ def lib():
         L.gq_version.restype = C.c_char_p
         L.gq_last_error.restype = C.c_char_p
         for f in ("gq_open", "gq_get_timings", "gq_set_tile", "gq_reads_upload", "gq_reads_wrap_device", "gq_reads_get_info",
-                  "gq_reads_rederive",
+                  "gq_reads_rederive", "gq_reads_rebuild_md", "gq_md_rebuild_spans", "gq_reads_missing_md",
                   "gq_germline_threshold", "gq_germline_threshold_device", "gq_pileup_counts", "gq_somatic_standard",
                   "gq_reference_upload", "gq_somatic_standard_ref", "gq_variant_support", "gq_vaf_histogram",
                   "gq_germline_standard", "gq_allele_evidence", "gq_genotype_likelihoods_call",
@@ -323,6 +328,10 @@ def lib():
         L.gq_free_somatic.argtypes = [C.POINTER(gq_somatic_calls)]
         L.gq_reads_free.argtypes = [C.c_void_p]
         L.gq_reads_rederive.argtypes = [C.c_void_p, C.c_void_p]
+        L.gq_reads_rebuild_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.POINTER(gq_md_rebuild_info)]
+        L.gq_md_rebuild_spans.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.gq_reads_missing_md.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.gq_close.argtypes = [C.c_void_p]
         vp = C.c_void_p
         for f in ("gq_bam_dev_open", "gq_bam_dev_scan", "gq_bam_dev_reads", "gq_reads_positions", "gq_reads_contig_begin",
@@ -456,6 +465,43 @@ class Context:
         """gq_reads_rederive: every derived structure of the resident read set dropped and the
         upload-time part derived again (the projection on the next call that reads it)."""
         _check(lib().gq_reads_rederive(self.h, reads.h))
+
+    def rebuild_md(self, reads: "DeviceReads", dref: "DeviceReference", recompute_all: bool = False) -> Dict[str, object]:
+        """gq_reads_rebuild_md: the resident read set's MD events rebuilt from the resident
+        reference, for the reads without a tag or (recompute_all) for every read, by
+        Read.fromSAMRecord's rule; the set is then derived again.  Raises what the host path
+        (reference.rebuild_md_tags, then the MD parse) raises, naming the read's index:
+        reference.ContigNotFound, ValueError (an N op), IndexError (an alignment past the contig's
+        or the read's end), soa.MdParseError (a reference byte no MD tag can hold); the read set
+        is then unchanged.  Returns rebuilt (reads), md_events (the new pool), ms (count + scan +
+        fill on the device) and the three spans."""
+        info = gq_md_rebuild_info()
+        rc = lib().gq_reads_rebuild_md(self.h, reads.h, dref.h, int(bool(recompute_all)), C.byref(info))
+        if rc != 0 and info.code:
+            msg = lib().gq_last_error().decode()
+            if info.code == 1:
+                from .reference import ContigNotFound
+                e = ContigNotFound("of read %d" % info.read, [])
+                e.msg = msg
+                e.args = (msg,)
+                raise e
+            if info.code == 2:
+                raise ValueError(msg)
+            if info.code == 3:
+                raise IndexError(msg)
+            from .soa import MdParseError
+            raise MdParseError(msg)
+        _check(rc)
+        spans = (C.c_float * 3)()
+        _check(lib().gq_md_rebuild_spans(self.h, spans))
+        return dict(rebuilt=int(info.rebuilt), md_events=int(info.md_events), ms=float(info.ms),
+                    count_ms=float(spans[0]), scan_ms=float(spans[1]), fill_ms=float(spans[2]))
+
+    def missing_md(self, reads: "DeviceReads") -> int:
+        """gq_reads_missing_md: reads of the resident set without MD events, counted on the device."""
+        out = C.c_int64()
+        _check(lib().gq_reads_missing_md(reads.h, C.byref(out)))
+        return int(out.value)
 
     def wrap_device(self, arrs: Dict[str, object]) -> "DeviceReads":
         s, keep = make_gq_reads(arrs)

@@ -607,6 +607,30 @@ typedef struct gq_reference gq_reference;
 gq_status gq_reference_upload(gq_ctx *ctx, int32_t n_contigs, const uint8_t *const *bases, const int64_t *lengths,
                               gq_reference **out);
 void gq_reference_free(gq_reference *ref);
+/* MD events rebuilt from the reference on the device (ReferenceGenome.buildMdTag,
+ * reference/ReferenceGenome.scala:41-47, by Read.fromSAMRecord's choice, reads/Read.scala:
+ * 223-247): reads without an MD tag (n_md < 0), or every read with recompute_all, get the events
+ * their alignment has against `ref` (a differing base on M/=/X: a mismatch; every base of a D: a
+ * deletion).  Any resident read set (gq_reads_upload, gq_reads_wrap_device, gq_bam_dev_reads).
+ * The set's md_off / n_md / n_mismatch / md_ev arrays and md_len are replaced, the upload-time
+ * structures derived again (gq_reads_rederive) and the projections dropped.  When no read needs
+ * a rebuild nothing changes and nothing is re-derived.  `ref` must have the set's number of
+ * contigs (GQ_E_ARG).  A failing read leaves the set as it was: info->read is the first one in
+ * resident order, info->code its first failing step in CIGAR order:
+ *   1 its contig is absent from the reference (ContigNotFound)                     GQ_E_ARG
+ *   2 a reference-consuming op other than M/=/X/D (N)                              GQ_E_ARG
+ *   3 an M/=/X/D op runs past the contig's end, or M/=/X past the read's sequence  GQ_E_ARG
+ *   4 an event's reference byte is not a letter (its MD string would not parse)    GQ_E_MD_PARSE
+ * info (may be NULL): read = -1 and code = 0 on success; rebuilt = reads given new events;
+ * md_events = the event pool's size afterwards; ms = the device span of count, scan and fill. */
+typedef struct { int64_t read; int32_t code; int32_t pad; int64_t rebuilt; int64_t md_events; float ms; } gq_md_rebuild_info;
+gq_status gq_reads_rebuild_md(gq_ctx *ctx, gq_dev_reads *r, const gq_reference *ref,
+                              int32_t recompute_all, gq_md_rebuild_info *info);
+/* Reads of the resident set without MD events (n_md < 0), counted on the device. */
+gq_status gq_reads_missing_md(const gq_dev_reads *r, int64_t *out);
+/* The last rebuild's spans on this context, HIP events (ms): count, scan, fill; zeros when that
+ * call rebuilt nothing or failed. */
+gq_status gq_md_rebuild_spans(const gq_ctx *ctx, float *out3);
 /* gq_somatic_standard with pileupFlatMapTwoRDDs' referenceGenome argument
  * (DistributedUtil.scala:316-335): every pileup's reference base is the reference's
  * (DistributedUtil.scala:266-268) instead of the reads' MD-derived one.  ref == NULL is
