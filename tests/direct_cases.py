@@ -1,5 +1,6 @@
 """Read sets and reference models for the tests of germline_direct / somatic_direct
-(test_gpu_tile_loop, test_gpu_counter_widths, test_somatic_bound_model, test_gpu_somatic_bound).
+(test_gpu_tile_loop, test_gpu_counter_widths, test_somatic_bound_model, test_gpu_somatic_bound) and,
+through proj_cases, of the projection kernels (test_gpu_proj_paths).
 
 * ``Reads``: read templates with a repeat count, expanded with numpy straight into a ReadSet
   (a million stacked reads in well under a second; make_read dicts are far too slow for that).
@@ -118,6 +119,110 @@ def knife_edge(n: int):
             best = (slack, thr1 - 1, alt)
     assert best is not None
     return best[1], best[2]
+
+
+# ---------------------------------------------------------------------------------------------
+# stacks on the percent knife edge (test_gpu_counter_widths, the projection cases)
+# ---------------------------------------------------------------------------------------------
+REF_OF = {"A": "G", "C": "A", "T": "C", "G": "T"}  # the MD (reference) base under each read base
+# the event's locus within its block: column offsets 0, 3, 7, and the first locus of the next
+# block with the reads starting in this one
+PLACES = (96, 99, 103, T)
+ISSUE_PAIRS = {240: (9, 24), 255: (19, 51), 256: (24, 64)}
+
+
+def stack(reads, loci, B, place, base, n, alt):
+    """n reads of 8 bases starting 3 before the event locus; alt of them carry `base` there."""
+    lx = B + place
+    s = lx - 3
+    r = REF_OF[base]
+    seq = ref_seq(s, s + 8)
+    if n > alt:
+        reads.add(s, seq[:3] + r + seq[4:], "8M", "8", n - alt)
+    if alt:
+        reads.add(s, seq[:3] + base + seq[4:], "8M", "3%s4" % r, alt)
+    loci.append((s - 1, s + 9))
+    return lx
+
+
+def segmented(reads, s, k, count=1):
+    """Reads of `1M1D` k times and a last 1M from s: k + 1 count segments (runs) each."""
+    ref = ref_seq(s, s + 2 * k + 1)
+    seq = ref[0::2]
+    md = "".join("1^%s" % ref[2 * j + 1] for j in range(k)) + "1"
+    reads.add(s, seq, "1M1D" * k + "1M", md, count)
+
+
+# ---------------------------------------------------------------------------------------------
+# tiles of eight kinds, a kind per tile (test_gpu_tile_loop, the projection cases)
+# ---------------------------------------------------------------------------------------------
+N_TILES = 16384
+KINDS = "abcdefgh"
+
+
+def tile_kinds(n=N_TILES, seed=20261020):
+    """A kind per tile, a..g drawn from a seeded RNG; h (deep) placed by hand, at most 40: before
+    and after every kind four tiles apart (consecutive tiles of one wave) and after itself."""
+    rng = np.random.default_rng(seed)
+    kinds = [KINDS[k] for k in rng.integers(0, 7, n)]
+    p = 64
+    for rep in range(2):
+        for x in "abcdefg":
+            kinds[p], kinds[p + 4] = "h", x
+            kinds[p + 32], kinds[p + 36] = x, "h"
+            p += 64 + 8 * rep
+        kinds[p], kinds[p + 4] = "h", "h"
+        p += 64
+    return kinds
+
+
+def tile_offsets(n, seed):
+    """Each tile's range start within its block, drawn from 16 values (every column offset twice):
+    a wave's next tile then has its range on the SAME block-relative loci once in 16, which is
+    where a word left dirty by the tile before (LDS words are indexed by block-relative locus)
+    changes a record instead of lying outside the range."""
+    return 16 + 29 * np.random.default_rng(seed).integers(0, 16, n)
+
+
+def germline_tiles(kinds):
+    """Tile i in block 2 i + 1 (the even blocks stay uncalled), a three-locus range each."""
+    reads, loci = Reads(), []
+    offs = tile_offsets(len(kinds), 7)
+    for i, kind in enumerate(kinds):
+        B = T * (2 * i + 1)
+        P = B + int(offs[i])
+        loci.append((P, P + 3))
+        alt = ref_base(P + 2)  # (differs from locus P + 1's base)
+        if kind == "a":  # plain reads and a SNV: a record pair
+            reads.plain(P - 3, 10, 2)
+            reads.snv(P - 3, 10, P + 1, alt, 2)
+        elif kind == "b":  # a byte other than A C G T N: the walker's.  The tile leaves every kind of word
+            # dirty on that exit: event counts at P (ev), MD bits (mk), a MidDeletion over P + 2 (dl)
+            s = ref_seq(P - 3, P + 7)
+            reads.plain(P - 3, 10, 2)
+            reads.snv(P - 3, 10, P, ref_base(P + 1), 2)
+            reads.snv(P - 3, 10, P + 1, "R", 1)
+            reads.add(P - 3, s[:4] + s[6:], "4M2D4M", "4^%s4" % s[4:6], 1)
+        elif kind == "c":  # a general CIGAR: an insertion after P, a deletion of P + 2
+            s = ref_seq(P - 3, P + 7)
+            reads.plain(P - 3, 10, 1)
+            reads.add(P - 3, s[:4] + "TT" + s[4:5] + s[6:], "4M2I1M1D4M", "5^%s4" % s[5], 2)
+        elif kind == "d":  # a MidDeletion across the range
+            s = ref_seq(P - 3, P + 7)
+            reads.plain(P - 3, 10, 1)
+            reads.add(P - 3, s[:2] + s[8:], "2M6D2M", "2^%s2" % s[2:8], 2)
+        elif kind == "e":  # no read reaches the tile
+            pass
+        elif kind == "f":  # MD events in the tile, none at the range's loci
+            reads.snv(P - 8, 24, P - 5, ref_base(P - 4), 2)
+            reads.snv(P - 8, 24, P + 9, ref_base(P + 10), 2)
+        elif kind == "g":  # a read without MD in the uncalled block after this one
+            reads.plain(P - 3, 10, 3)
+            reads.add(B + T + 40, ref_seq(B + T + 40, B + T + 50), "10M", None)
+        elif kind == "h":  # 256+ stacked reads: the deep instantiation's
+            reads.plain(P - 3, 10, 200)
+            reads.snv(P - 3, 10, P + 1, alt, 60 + i % 8)
+    return reads.build(T * (2 * len(kinds) + 2)), ranges(loci)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -267,3 +372,28 @@ def predicted_candidates(held, min_mapq=1):
         certain += c in ("keep", "none")
         possible += c == "knife"
     return certain, possible
+
+
+def none_tiles(n_tiles=64):
+    """Tiles T apart, each with three 'drop' cases (39 matching reads and one mismatch); every third
+    tile also holds a matching read with one quality >= 128 (a term without a byte) elsewhere in
+    its range.  -> (tumor, normal, loci, the drop cases in the tiles that hold such a byte)."""
+    tumor, normal = Reads(), Reads()
+    loci, expect = [], 0
+    for i in range(n_tiles):
+        B = T * (i + 1)
+        with_none = i % 3 == 0
+        for x in (40, 200, 330):  # three 'drop' cases: 39 matching reads and one mismatch
+            s = B + x - 20
+            tumor.plain(s, 50, 39, qual=30, mapq=60)
+            tumor.snv(s, 50, B + x, ref_base(B + x + 1), 1, qual=30, mapq=60)
+            normal.plain(s, 50, 5)
+            expect += with_none
+        if with_none:  # a matching read elsewhere in the tile's range, one quality past the table
+            tumor.add(B + 100, ref_seq(B + 100, B + 110), "10M", "10", qual=[30] * 4 + [128 + i % 100] + [30] * 5,
+                      mapq=60)
+            normal.plain(B + 100, 10, 5)
+        loci.append((B + 30, B + 340))
+    assert classify([(30, 60, False)] + [(30, 60, True)] * 39)[0] == "drop"
+    L = T * (n_tiles + 2)
+    return tumor.build(L), normal.build(L), ranges(loci), expect

@@ -15,25 +15,8 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-REF_OF = {"A": "G", "C": "A", "T": "C", "G": "T"}  # the MD (reference) base under each read base
-# the event's locus within its block: column offsets 0, 3, 7, and the first locus of the next
-# block with the reads starting in this one
-PLACES = (96, 99, 103, dc.T)
-ISSUE_PAIRS = {240: (9, 24), 255: (19, 51), 256: (24, 64)}
-
-
-def _stack(reads, loci, B, place, base, n, alt):
-    """n reads of 8 bases starting 3 before the event locus; alt of them carry `base` there."""
-    lx = B + place
-    s = lx - 3
-    r = REF_OF[base]
-    seq = dc.ref_seq(s, s + 8)
-    if n > alt:
-        reads.add(s, seq[:3] + r + seq[4:], "8M", "8", n - alt)
-    if alt:
-        reads.add(s, seq[:3] + base + seq[4:], "8M", "3%s4" % r, alt)
-    loci.append((s - 1, s + 9))
-    return lx
+REF_OF, PLACES, ISSUE_PAIRS = dc.REF_OF, dc.PLACES, dc.ISSUE_PAIRS  # (shared with the projection cases)
+_stack, _segmented = dc.stack, dc.segmented
 
 
 def _run(gpu_ctx, reads, loci, threshold, n_blocks):
@@ -100,14 +83,6 @@ def test_all_255_reads_carry_the_event(gpu_ctx):
 # ---------------------------------------------------------------------------------------------
 # slot chunks: a chunk holds kSlots = 256 runs; a round is 64 window reads (a lane each)
 # ---------------------------------------------------------------------------------------------
-def _segmented(reads, s, k, count=1):
-    """Reads of `1M1D` k times and a last 1M from s: k + 1 count segments (runs) each."""
-    ref = dc.ref_seq(s, s + 2 * k + 1)
-    seq = ref[0::2]
-    md = "".join("1^%s" % ref[2 * j + 1] for j in range(k)) + "1"
-    reads.add(s, seq, "1M1D" * k + "1M", md, count)
-
-
 @pytest.mark.parametrize("n_reads,k,walk", [(64, 3, 0), (65, 3, 0), (64, 4, 1)], ids=["256_runs", "260_runs", "320_runs"])
 def test_runs_of_one_round_against_the_chunk(gpu_ctx, n_reads, k, walk):
     """64 reads of 4 runs fill a chunk exactly and stay on the kernel.  A 65th such read is the

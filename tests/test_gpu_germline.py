@@ -171,8 +171,8 @@ def test_cli_adam_read_input_equals_sam(tmp_path):
 
 
 def test_synthetic_column_path_dense_outputs(gpu_ctx):
-    """emit_ref / emit_no_call through the column kernel (HomRef / NoCall rows inline,
-    variant candidates through germline_expand); the column kernel keeps nearly every tile."""
+    """emit_ref / emit_no_call through germline_direct, the default pileup kernel (HomRef / NoCall
+    rows inline, variant candidates through germline_expand); it keeps nearly every tile."""
     g = generate(60_000, 30, seed=7, indel_rate=3e-4)
     rs = g.to_read_set()
     loci = _loci(rs)
@@ -185,8 +185,8 @@ def test_synthetic_column_path_dense_outputs(gpu_ctx):
 
 
 def test_chrm_subsampled_column_path(gpu_ctx, chrm):
-    """Real reads (29-80 bp, real MD tags) at a depth whose tiles fit the column kernel's stage
-    (every 8th read of chrM.sorted.bam: about 18x)."""
+    """Real reads (29-80 bp, real MD tags) at about 18x (every 8th read of chrM.sorted.bam)
+    through germline_direct, the default pileup kernel."""
     from guacamole_amd.reads import ReadSet
     sub = chrm.subset(np.arange(0, chrm.n, 8))
     loci = _loci(sub)
@@ -195,7 +195,7 @@ def test_chrm_subsampled_column_path(gpu_ctx, chrm):
         want = O.germline_threshold(sub, loci, t, er, enc)
         assert got == want
     tm = gpu_ctx.timings()
-    assert tm["walk_tiles"] < tm["tiles"] // 2, tm  # most tiles through the column kernel
+    assert tm["walk_tiles"] < tm["tiles"] // 2, tm  # most tiles stay on germline_direct
 
 
 class _DeviceArray:
@@ -249,9 +249,10 @@ def test_wrapped_device_reads_unordered_pool(gpu_ctx):
 
 
 def test_deep_panel_500x_germline(gpu_ctx):
-    """BASELINE configs[4] depth (500x, a targeted-panel region): blocks of ~550 projection rows
-    (16-bit counts past 240 rows) stay on germline_proj, none goes to the walker; calls
-    identical to the oracle."""
+    """BASELINE configs[4] depth (500x, a targeted-panel region): windows of ~550 reads (past
+    kShallow = 255: the deep instantiation's 16-bit counts) stay on germline_direct, none goes to
+    the walker; calls identical to the oracle.  (The same read set through germline_proj, blocks
+    of ~550 projection rows: test_gpu_proj_paths.test_deep_panel_500x_stays_on_germline_proj.)"""
     g = generate(12_000, 500.0, seed=5, indel_rate=3e-4)
     rs = g.to_read_set()
     loci = _loci(rs)
@@ -319,13 +320,21 @@ def test_rederive_gives_the_same_records(gpu_ctx):
     reads = gpu_ctx.upload(g.arrays)
     loci = (np.array([0], np.int32), np.array([0], np.int64), np.array([119_999], np.int64), np.array([0], np.int64))
     want = gpu_ctx.germline_threshold(reads, loci, 8).tuples(g.contig_names)
+    # germline-threshold counts straight from the reads (germline_direct) and derives no
+    # projection; germline-standard always does (gq_germline_standard: ensure_projection), so the
+    # sizes compared below are a real projection's
+    std = gpu_ctx.germline_standard(reads, loci).rows
+    assert std
     st0 = gpu_ctx.proj_stats(reads)
+    assert st0["projected"] == 1 and st0["proj_bytes"] > 0 and st0["pev_count"] > 0 and st0["n_rows"] > 0
     for _ in range(2):
         gpu_ctx.rederive(reads)
         st = gpu_ctx.proj_stats(reads)
         assert st["projected"] == 0
         assert gpu_ctx.germline_threshold(reads, loci, 8).tuples(g.contig_names) == want
+        assert repr(gpu_ctx.germline_standard(reads, loci).rows) == repr(std)  # (repr: a NaN equals itself)
         st = gpu_ctx.proj_stats(reads)
+        assert st["projected"] == 1 and st["proj_bytes"] > 0
         assert (st["proj_bytes"], st["pev_count"], st["n_rows"]) == (st0["proj_bytes"], st0["pev_count"], st0["n_rows"])
     t = generate(100_000, 60, seed=3, somatic_rate=2e-4, tumor=True, read_seed=11)
     n = generate(100_000, 30, seed=3, somatic_rate=2e-4, tumor=False, read_seed=12)

@@ -92,27 +92,7 @@ def test_none_element_turns_off_its_tile_only(gpu_ctx):
     locus of the tile becomes a candidate, 'drop' cases included; the tiles without one drop theirs.
     (64 tiles: a tile per wave.  The flag leaking into the SAME wave's next tile is
     test_gpu_tile_loop.test_somatic_16384_tiles' matter.)"""
-    tumor, normal = dc.Reads(), dc.Reads()
-    loci, expect = [], 0
-    n_tiles = 64
-    for i in range(n_tiles):
-        B = dc.T * (i + 1)
-        with_none = i % 3 == 0
-        for x in (40, 200, 330):  # three 'drop' cases: 39 matching reads and one mismatch
-            s = B + x - 20
-            tumor.plain(s, 50, 39, qual=30, mapq=60)
-            tumor.snv(s, 50, B + x, dc.ref_base(B + x + 1), 1, qual=30, mapq=60)
-            normal.plain(s, 50, 5)
-            expect += with_none
-        if with_none:  # a matching read elsewhere in the tile's range, one quality past the table
-            tumor.add(B + 100, dc.ref_seq(B + 100, B + 110), "10M", "10", qual=[30] * 4 + [128 + i % 100] + [30] * 5,
-                      mapq=60)
-            normal.plain(B + 100, 10, 5)
-        loci.append((B + 30, B + 340))
-    assert dc.classify([(30, 60, False)] + [(30, 60, True)] * 39)[0] == "drop"
-    L = dc.T * (n_tiles + 2)
-    t, n = tumor.build(L), normal.build(L)
-    loci = dc.ranges(loci)
+    t, n, loci, expect = dc.none_tiles(64)  # (shared with the projection cases)
     calls = gpu_ctx.somatic_standard(device_reads(gpu_ctx, t), device_reads(gpu_ctx, n), loci, **PARAMS)
     tm = gpu_ctx.timings()
     print("none tiles: candidate_loci %d, expected %d, walk_tiles %d" % (calls.candidate_loci, expect, tm["walk_tiles"]))

@@ -15,73 +15,9 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-N_TILES = 16384
-KINDS = "abcdefgh"
-
-
-def tile_kinds(n=N_TILES, seed=20261020):
-    """A kind per tile, a..g drawn from a seeded RNG; h (deep) placed by hand, at most 40: before
-    and after every kind four tiles apart (consecutive tiles of one wave) and after itself."""
-    rng = np.random.default_rng(seed)
-    kinds = [KINDS[k] for k in rng.integers(0, 7, n)]
-    p = 64
-    for rep in range(2):
-        for x in "abcdefg":
-            kinds[p], kinds[p + 4] = "h", x
-            kinds[p + 32], kinds[p + 36] = x, "h"
-            p += 64 + 8 * rep
-        kinds[p], kinds[p + 4] = "h", "h"
-        p += 64
-    return kinds
-
-
-def tile_offsets(n, seed):
-    """Each tile's range start within its block, drawn from 16 values (every column offset twice):
-    a wave's next tile then has its range on the SAME block-relative loci once in 16, which is
-    where a word left dirty by the tile before (LDS words are indexed by block-relative locus)
-    changes a record instead of lying outside the range."""
-    return 16 + 29 * np.random.default_rng(seed).integers(0, 16, n)
-
-
-def germline_tiles(kinds):
-    """Tile i in block 2 i + 1 (the even blocks stay uncalled), a three-locus range each."""
-    reads, loci = dc.Reads(), []
-    offs = tile_offsets(len(kinds), 7)
-    for i, kind in enumerate(kinds):
-        B = dc.T * (2 * i + 1)
-        P = B + int(offs[i])
-        loci.append((P, P + 3))
-        alt = dc.ref_base(P + 2)  # (differs from locus P + 1's base)
-        if kind == "a":  # plain reads and a SNV: a record pair
-            reads.plain(P - 3, 10, 2)
-            reads.snv(P - 3, 10, P + 1, alt, 2)
-        elif kind == "b":  # a byte other than A C G T N: the walker's.  The tile leaves every kind of word
-            # dirty on that exit: event counts at P (ev), MD bits (mk), a MidDeletion over P + 2 (dl)
-            s = dc.ref_seq(P - 3, P + 7)
-            reads.plain(P - 3, 10, 2)
-            reads.snv(P - 3, 10, P, dc.ref_base(P + 1), 2)
-            reads.snv(P - 3, 10, P + 1, "R", 1)
-            reads.add(P - 3, s[:4] + s[6:], "4M2D4M", "4^%s4" % s[4:6], 1)
-        elif kind == "c":  # a general CIGAR: an insertion after P, a deletion of P + 2
-            s = dc.ref_seq(P - 3, P + 7)
-            reads.plain(P - 3, 10, 1)
-            reads.add(P - 3, s[:4] + "TT" + s[4:5] + s[6:], "4M2I1M1D4M", "5^%s4" % s[5], 2)
-        elif kind == "d":  # a MidDeletion across the range
-            s = dc.ref_seq(P - 3, P + 7)
-            reads.plain(P - 3, 10, 1)
-            reads.add(P - 3, s[:2] + s[8:], "2M6D2M", "2^%s2" % s[2:8], 2)
-        elif kind == "e":  # no read reaches the tile
-            pass
-        elif kind == "f":  # MD events in the tile, none at the range's loci
-            reads.snv(P - 8, 24, P - 5, dc.ref_base(P - 4), 2)
-            reads.snv(P - 8, 24, P + 9, dc.ref_base(P + 10), 2)
-        elif kind == "g":  # a read without MD in the uncalled block after this one
-            reads.plain(P - 3, 10, 3)
-            reads.add(B + dc.T + 40, dc.ref_seq(B + dc.T + 40, B + dc.T + 50), "10M", None)
-        elif kind == "h":  # 256+ stacked reads: the deep instantiation's
-            reads.plain(P - 3, 10, 200)
-            reads.snv(P - 3, 10, P + 1, alt, 60 + i % 8)
-    return reads.build(dc.T * (2 * len(kinds) + 2)), dc.ranges(loci)
+# (the builders are shared with the projection cases: direct_cases)
+N_TILES, KINDS = dc.N_TILES, dc.KINDS
+tile_kinds, tile_offsets, germline_tiles = dc.tile_kinds, dc.tile_offsets, dc.germline_tiles
 
 
 def test_every_pair_of_kinds_meets_on_one_wave():
