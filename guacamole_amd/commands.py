@@ -1290,11 +1290,36 @@ def _finish_rank(rc: int) -> int:
     return rc
 
 
+def structural_variant_main(argv: Sequence[str]) -> int:
+    """StructuralVariant.Caller.run (commands/StructuralVariantCaller.scala:273-287): the ranges
+    where discordant first-in-pair reads give evidence of a large deletion, one line per contig
+    with an exceptional pair (saveAsTextFile layout)."""
+    from . import structural
+    p = argparse.ArgumentParser(prog="structural-variant", description="Find structural variants, e.g. large deletions.")
+    p.add_argument("--reads", required=True, help="Aligned reads (BAM)")
+    p.add_argument("--output", required=True, help="Path to output text file (a directory with part-00000)")
+    p.add_argument("--filter-contig", default="", help="(accepted and ignored, as the reference's run never reads it)")
+    p.add_argument("--out-tsv", default="", help="Also write contig, start, stop, pairs, wiggle per deletion")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("structural-variant")
+    ctx = native.Context(args.device)
+    res = structural.structural_variant(ctx, args.reads)
+    s = res["stats"]
+    print("insert stats: MedianStats(%r,%r)" % (s["median"], s["mad"]))
+    structural.write_output(args.output, structural.text_lines(res["node_contigs"], res["cliques"],
+                                                               res["contig_names"]))
+    if args.out_tsv:
+        with open(args.out_tsv, "w") as fh:
+            fh.writelines(l + "\n" for l in structural.tsv_lines(res["cliques"], res["contig_names"]))
+    return 0
+
+
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
-            "pileup-counts": pileup_counts_main}
+            "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -11,7 +11,7 @@
 //   rec_hop        thread / block: record count and landing offset from a start; the host
 //                  checks that each block's chain lands on the next block's start and re-hops
 //                  a block from the true chain where it does not (a false sync)
-//   rec_list       thread / block: the record offsets
+//   rec_list       thread / block: the record offsets (record_list: also gq_sv_pairs_from_bam's start)
 //   rec_parse      thread / record: fields, aux (MD, RG), Read.InputFilters, MD event count
 //   rec_fill       16 lanes / kept record: the SoA scalars, sequence (4-bit -> ASCII),
 //                  qualities, CIGAR, MD events
@@ -35,6 +35,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -950,6 +951,8 @@ struct gq_bam_dev {
   DevBuf rec, info, kidx, seq_o, cig_o, md_o;
   int64_t n_rec = 0, n_keep = 0, seq_bytes = 0, cigar_len = 0, md_events = 0;
   bool scanned = false;
+  bool listed = false;  // b->rec holds this load's record offsets (record_list)
+  int64_t n_listed = 0;
   gq_bam_dev_sizes sizes{};
   ~gq_bam_dev() {
     for (DevBuf *b : {&comp, &blk, &out, &scratch, &status, &rec, &info, &kidx, &seq_o, &cig_o, &md_o}) b->release();
@@ -1234,6 +1237,107 @@ bool voff_pos(const gq_bam_dev *b, uint64_t v, int64_t &blk, int64_t &off) {
   if (uo > (int64_t)b->blocks[(size_t)blk].isize) return false;
   stream_pos(b, b->blocks[(size_t)blk].out_off + uo, blk, off);
   return true;
+}
+
+// The record offset list of the loaded stream (b->rec, n_rec entries, file order): candidate
+// starts per block, chains, the host walk of the true chain.  gq_bam_dev_scan and
+// gq_sv_pairs_from_bam start from it; a list already made for this load is kept.
+gq_status record_list(gq_bam_dev *b, int64_t *n_rec_out) {
+  if (b->listed) {
+    *n_rec_out = b->n_listed;
+    return GQ_OK;
+  }
+  gq_ctx *c = b->ctx;
+  const int32_t n_ref = (int32_t)b->names.size();
+  auto t0 = std::chrono::steady_clock::now();
+  const uint8_t *d = (const uint8_t *)b->out.p;
+  const int64_t n = b->n_out, nb = (int64_t)b->sel.size();
+  const BgzfBlock *blk = (const BgzfBlock *)b->blk.p;
+  // record boundaries: candidate starts per block, chains, the host walk of the true chain
+  DevBuf first, cnt, land, base;
+  const size_t nbb = sizeof(int64_t) * (size_t)(nb + 1);
+  HIP_TRY(first.ensure(nbb));
+  HIP_TRY(cnt.ensure(nbb));
+  HIP_TRY(land.ensure(nbb));
+  HIP_TRY(base.ensure(nbb));
+  if (nb) {
+    hipLaunchKernelGGL(rec_sync, dim3(grid(nb, 4)), dim3(256), 0, c->stream, d, n, blk, nb, b->planned ? 0 : b->rec0, n_ref,
+                       (int64_t *)first.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rec_hop, dim3(grid(nb, 256)), dim3(256), 0, c->stream, d, n, blk, (int64_t)0, nb,
+                       (const int64_t *)first.p, (int64_t *)cnt.p, (int64_t *)land.p);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int64_t> hf((size_t)nb), hc((size_t)nb), hl((size_t)nb);
+  if (nb) {
+    HIP_TRY(hipMemcpyAsync(hf.data(), first.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hc.data(), cnt.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hl.data(), land.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  // the true chain, segment by segment (an unplanned load: one segment from the first record
+  // to the stream's end)
+  const std::vector<BgzfBlock> &sel = b->sel;
+  int64_t n_rec = 0;
+  int64_t rehops = 0;
+  const size_t n_seg = b->planned ? b->segs.size() : 1;
+  for (size_t s = 0; s < n_seg; ++s) {
+    const int64_t k0 = b->planned ? b->sel_seg0[s] : 0, k1 = b->planned ? b->sel_seg0[s + 1] : nb;
+    const bool eof = b->planned ? b->segs[s].eof : true;
+    const int64_t kr = eof ? k1 : k1 - 1;  // blocks whose records are read (the last one only completes a record)
+    int64_t at = b->planned ? sel[(size_t)k0].out_off + b->segs[s].first : b->rec0;
+    for (int64_t k = k0; k < k1; ++k) {
+      const int64_t hi = sel[(size_t)k].out_off + (int64_t)sel[(size_t)k].isize;
+      if (k >= kr || at >= hi) {  // no record of the chain starts in this block
+        hf[(size_t)k] = -1;
+        hc[(size_t)k] = 0;
+        continue;
+      }
+      if (hf[(size_t)k] != at || hl[(size_t)k] < 0) {  // a false sync (or none): re-hop from the chain
+        ++rehops;
+        hf[(size_t)k] = at;
+        HIP_TRY(hipMemcpyAsync((int64_t *)first.p + k, &at, sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(rec_hop, dim3(1), dim3(64), 0, c->stream, d, n, blk, k, k + 1, (const int64_t *)first.p,
+                           (int64_t *)cnt.p, (int64_t *)land.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&hc[(size_t)k], (int64_t *)cnt.p + k, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&hl[(size_t)k], (int64_t *)land.p + k, sizeof(int64_t), hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (hl[(size_t)k] < 0)
+          return set_err(GQ_E_BAM_FORMAT, "truncated BAM record %lld", (long long)(n_rec + hc[(size_t)k]));
+      }
+      n_rec += hc[(size_t)k];
+      at = hl[(size_t)k];
+    }
+    const int64_t seg_end = sel[(size_t)k1 - 1].out_off + (int64_t)sel[(size_t)k1 - 1].isize;
+    if (eof && at != seg_end) return set_err(GQ_E_BAM_FORMAT, "truncated BAM record %lld", (long long)n_rec);
+    if (!eof && at > seg_end)
+      return set_err(GQ_E_PLAN, "a BAM record runs past the end of planned segment %lld", (long long)s);
+  }
+  std::vector<int64_t> hb((size_t)nb + 1, 0);
+  for (int64_t k = 0; k < nb; ++k) hb[(size_t)k + 1] = hb[(size_t)k] + hc[(size_t)k];
+  if (nb) {
+    HIP_TRY(hipMemcpyAsync(first.p, hf.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(base.p, hb.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(b->rec.ensure(sizeof(int64_t) * (size_t)(n_rec + 1)));
+  if (nb) {
+    hipLaunchKernelGGL(rec_list, dim3(grid(nb, 256)), dim3(256), 0, c->stream, d, blk, nb, (const int64_t *)first.p,
+                       (const int64_t *)base.p, (int64_t *)b->rec.p);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  b->sizes.records_ms = ms_since(t0);
+  first.release();
+  cnt.release();
+  land.release();
+  base.release();
+  (void)rehops;
+  b->listed = true;
+  b->n_listed = n_rec;
+  *n_rec_out = n_rec;
+  return GQ_OK;
 }
 
 }  // namespace
@@ -1697,88 +1801,13 @@ gq_status gq_bam_dev_scan(gq_bam_dev *b, const gq_bam_dev_filters *fl, int64_t *
   b->scanned = false;
   auto t0 = std::chrono::steady_clock::now();
   const uint8_t *d = (const uint8_t *)b->out.p;
-  const int64_t n = b->n_out, nb = (int64_t)b->sel.size();
-  const BgzfBlock *blk = (const BgzfBlock *)b->blk.p;
-  // record boundaries: candidate starts per block, chains, the host walk of the true chain
-  DevBuf first, cnt, land, base, tmp;
-  const size_t nbb = sizeof(int64_t) * (size_t)(nb + 1);
-  HIP_TRY(first.ensure(nbb));
-  HIP_TRY(cnt.ensure(nbb));
-  HIP_TRY(land.ensure(nbb));
-  HIP_TRY(base.ensure(nbb));
-  if (nb) {
-    hipLaunchKernelGGL(rec_sync, dim3(grid(nb, 4)), dim3(256), 0, c->stream, d, n, blk, nb, b->planned ? 0 : b->rec0, n_ref,
-                       (int64_t *)first.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rec_hop, dim3(grid(nb, 256)), dim3(256), 0, c->stream, d, n, blk, (int64_t)0, nb,
-                       (const int64_t *)first.p, (int64_t *)cnt.p, (int64_t *)land.p);
-    HIP_TRY(hipGetLastError());
-  }
-  std::vector<int64_t> hf((size_t)nb), hc((size_t)nb), hl((size_t)nb);
-  if (nb) {
-    HIP_TRY(hipMemcpyAsync(hf.data(), first.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hc.data(), cnt.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hl.data(), land.p, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  // the true chain, segment by segment (an unplanned load: one segment from the first record
-  // to the stream's end)
-  const std::vector<BgzfBlock> &sel = b->sel;
+  const int64_t n = b->n_out;
   int64_t n_rec = 0;
-  int64_t rehops = 0;
-  const size_t n_seg = b->planned ? b->segs.size() : 1;
-  for (size_t s = 0; s < n_seg; ++s) {
-    const int64_t k0 = b->planned ? b->sel_seg0[s] : 0, k1 = b->planned ? b->sel_seg0[s + 1] : nb;
-    const bool eof = b->planned ? b->segs[s].eof : true;
-    const int64_t kr = eof ? k1 : k1 - 1;  // blocks whose records are read (the last one only completes a record)
-    int64_t at = b->planned ? sel[(size_t)k0].out_off + b->segs[s].first : b->rec0;
-    for (int64_t k = k0; k < k1; ++k) {
-      const int64_t hi = sel[(size_t)k].out_off + (int64_t)sel[(size_t)k].isize;
-      if (k >= kr || at >= hi) {  // no record of the chain starts in this block
-        hf[(size_t)k] = -1;
-        hc[(size_t)k] = 0;
-        continue;
-      }
-      if (hf[(size_t)k] != at || hl[(size_t)k] < 0) {  // a false sync (or none): re-hop from the chain
-        ++rehops;
-        hf[(size_t)k] = at;
-        HIP_TRY(hipMemcpyAsync((int64_t *)first.p + k, &at, sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(rec_hop, dim3(1), dim3(64), 0, c->stream, d, n, blk, k, k + 1, (const int64_t *)first.p,
-                           (int64_t *)cnt.p, (int64_t *)land.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&hc[(size_t)k], (int64_t *)cnt.p + k, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&hl[(size_t)k], (int64_t *)land.p + k, sizeof(int64_t), hipMemcpyDeviceToHost,
-                               c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hl[(size_t)k] < 0)
-          return set_err(GQ_E_BAM_FORMAT, "truncated BAM record %lld", (long long)(n_rec + hc[(size_t)k]));
-      }
-      n_rec += hc[(size_t)k];
-      at = hl[(size_t)k];
-    }
-    const int64_t seg_end = sel[(size_t)k1 - 1].out_off + (int64_t)sel[(size_t)k1 - 1].isize;
-    if (eof && at != seg_end) return set_err(GQ_E_BAM_FORMAT, "truncated BAM record %lld", (long long)n_rec);
-    if (!eof && at > seg_end)
-      return set_err(GQ_E_PLAN, "a BAM record runs past the end of planned segment %lld", (long long)s);
+  DevBuf tmp;
+  {
+    const gq_status rs = record_list(b, &n_rec);
+    if (rs) return rs;
   }
-  std::vector<int64_t> hb((size_t)nb + 1, 0);
-  for (int64_t k = 0; k < nb; ++k) hb[(size_t)k + 1] = hb[(size_t)k] + hc[(size_t)k];
-  if (nb) {
-    HIP_TRY(hipMemcpyAsync(first.p, hf.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base.p, hb.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_TRY(b->rec.ensure(sizeof(int64_t) * (size_t)(n_rec + 1)));
-  if (nb) {
-    hipLaunchKernelGGL(rec_list, dim3(grid(nb, 256)), dim3(256), 0, c->stream, d, blk, nb, (const int64_t *)first.p,
-                       (const int64_t *)base.p, (int64_t *)b->rec.p);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  b->sizes.records_ms = ms_since(t0);
-  first.release();
-  cnt.release();
-  land.release();
-  base.release();
   // parse + filter every record
   t0 = std::chrono::steady_clock::now();
   DevFilters f{};
@@ -1924,7 +1953,6 @@ gq_status gq_bam_dev_scan(gq_bam_dev *b, const gq_bam_dev_filters *fl, int64_t *
   b->sizes.seq_bytes = b->seq_bytes;
   b->sizes.cigar_len = b->cigar_len;
   b->sizes.md_events = b->md_events;
-  (void)rehops;
   b->scanned = true;
   *sizes = b->sizes;
   return GQ_OK;
@@ -2119,6 +2147,8 @@ gq_status gq_reads_download(const gq_dev_reads *r, const gq_reads *dst) {
 }
 
 }  // extern "C"
+
+#include "gq_structural.h"  // structural-variant (gq_sv_*): pairs from the record list, stats, graph
 
 namespace {
 __global__ void warm_k() {}

@@ -244,6 +244,23 @@ class gq_md_rebuild_info(C.Structure):
                 ("md_events", C.c_int64), ("ms", C.c_float)]
 
 
+class gq_sv_stats(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_in_range", C.c_int64), ("n_exceptional", C.c_int64),
+                ("median", C.c_double), ("mad", C.c_double), ("max_normal", C.c_int32), ("reserved", C.c_int32),
+                ("stats_ms", C.c_float), ("order_ms", C.c_float)]
+
+
+class gq_sv_graph(C.Structure):
+    _fields_ = [("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("i", C.POINTER(C.c_int32)),
+                ("j", C.POINTER(C.c_int32)), ("weight", C.POINTER(C.c_int64)), ("edge_ms", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class gq_sv_cliques(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int64)),
+                ("stop", C.POINTER(C.c_int64)), ("pairs", C.POINTER(C.c_int64)), ("wiggle", C.POINTER(C.c_int64))]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -259,7 +276,10 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_write_vcf_germline", "gq_allele_evidence", "gq_free_allele_evidence", "gq_genotype_likelihoods_call",
             "gq_free_genotype_likelihoods", "gq_pileup_elements_call", "gq_free_pileup_elements",
             "gq_somatic_likelihoods_call", "gq_free_somatic_likelihoods", "gq_pileup_counts_call",
-            "gq_free_pileup_counts", "gq_reads_rebuild_md", "gq_md_rebuild_spans", "gq_reads_missing_md")
+            "gq_free_pileup_counts", "gq_reads_rebuild_md", "gq_md_rebuild_spans", "gq_reads_missing_md",
+            "gq_sv_pairs_from_bam", "gq_sv_pairs_from_host", "gq_sv_pairs_count", "gq_sv_pairs_download",
+            "gq_sv_pairs_free", "gq_sv_stats_call", "gq_sv_select", "gq_sv_nodes_download", "gq_sv_graph_call",
+            "gq_sv_free_graph", "gq_sv_cliques_call", "gq_sv_free_cliques", "gq_sv_call")
 
 
 def lib():
@@ -366,6 +386,28 @@ def lib():
         L.gq_reads_positions.argtypes = [vp, vp, vp]
         L.gq_reads_contig_begin.argtypes = [vp, vp]
         L.gq_reads_download.argtypes = [vp, C.POINTER(gq_reads)]
+        for f in ("gq_sv_pairs_from_bam", "gq_sv_pairs_from_host", "gq_sv_pairs_download", "gq_sv_stats_call",
+                  "gq_sv_select", "gq_sv_nodes_download", "gq_sv_graph_call", "gq_sv_cliques_call", "gq_sv_call"):
+            getattr(L, f).restype = C.c_int
+        L.gq_sv_pairs_from_bam.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_float)]
+        L.gq_sv_pairs_from_host.argtypes = [vp, C.c_int64] + [vp] * 7 + [C.POINTER(vp)]
+        L.gq_sv_pairs_count.argtypes = [vp]
+        L.gq_sv_pairs_count.restype = C.c_int64
+        L.gq_sv_pairs_download.argtypes = [vp] * 8
+        L.gq_sv_pairs_free.argtypes = [vp]
+        L.gq_sv_pairs_free.restype = None
+        L.gq_sv_stats_call.argtypes = [vp, C.POINTER(gq_sv_stats)]
+        L.gq_sv_select.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        L.gq_sv_nodes_download.argtypes = [vp] * 6
+        L.gq_sv_graph_call.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(gq_sv_graph))]
+        L.gq_sv_free_graph.argtypes = [C.POINTER(gq_sv_graph)]
+        L.gq_sv_free_graph.restype = None
+        L.gq_sv_cliques_call.argtypes = [C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int32,
+                                         C.POINTER(C.POINTER(gq_sv_cliques))]
+        L.gq_sv_free_cliques.argtypes = [C.POINTER(gq_sv_cliques)]
+        L.gq_sv_free_cliques.restype = None
+        L.gq_sv_call.argtypes = [vp, C.POINTER(gq_sv_stats), C.POINTER(C.POINTER(gq_sv_cliques)),
+                                 C.POINTER(C.c_float), C.POINTER(C.c_float)]
         _lib = L
     return _lib
 

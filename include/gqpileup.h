@@ -747,6 +747,80 @@ gq_status gq_pileup_counts_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq
                                 const gq_pileup_counts_params *params, gq_pileup_count_rows **out);
 void gq_free_pileup_counts(gq_pileup_count_rows *res);
 
+/* structural-variant: large deletions from discordant read pairs (StructuralVariantCaller.scala).
+ * No pileup, MD tag or reference is involved; the input need not be sorted.  With len a record's
+ * own l_seq, lo / hi the smaller / larger of its start and its mate's start (0-based):
+ *   Min = lo, GapMin = lo + len, GapMax = hi, Max = hi + len, insertSize = hi - lo + len.
+ * Stages, each with its own call (tests and hosts with their own reader enter where they like):
+ *   pairs        records that are paired, mapped (the loader's isMapped), first in pair, not
+ *                duplicates, with a mapped mate and tlen != 0, in file order (resident SoA)
+ *   stats        in range: contig == mate_contig, strands differ, tlen < 25000 (raw);
+ *                oriented = tlen (forward) or -tlen (reverse); median and MAD over every in-range
+ *                pair (exact: even counts give the mean of the two middle values, none gives
+ *                0, 0); max_normal = (int)(median + 5 mad), truncated toward zero;
+ *                exceptional: in range and raw tlen > max_normal, ordered by (contig, lo), stable
+ *   graph        nodes = exceptional pairs in that order; for node i the successors j = i + 1 ...
+ *                on its contig up to the first with |GapMin_j - Min_i| > N; edge (i, j, weight
+ *                |(GapMax_j - Min_j) - (GapMax_i - Min_i)|) unless the pairs are incompatible
+ *   cliques      (host) one greedy clique per connected component with an edge: edges by
+ *                (weight, i, j), seeded with the first edge's i                              */
+typedef struct gq_sv_pairs gq_sv_pairs; /* resident pairs, and after stats / select the node set */
+typedef struct {
+  int64_t n_pairs, n_in_range, n_exceptional;
+  double median, mad;       /* of the oriented sizes of the in-range pairs                    */
+  int32_t max_normal;       /* (int)(median + 5 * mad)                                        */
+  int32_t reserved;
+  float stats_ms, order_ms; /* device spans: mask + sorts + statistics; compaction + ordering */
+} gq_sv_stats;
+typedef struct {
+  int64_t n_nodes, n_edges;
+  int32_t *i, *j;           /* node indexes in (contig, lo) order, i < j; by i then j         */
+  int64_t *weight;
+  float edge_ms;            /* device span of count + scan + fill                             */
+  int32_t reserved;
+} gq_sv_graph;
+typedef struct {
+  int64_t n;                /* cliques, by (contig, start, stop)                               */
+  int32_t *contig;
+  int64_t *start, *stop;    /* the deletion: max GapMin and min GapMax of the members          */
+  int64_t *pairs, *wiggle;  /* members; how far the deletion may shrink and still fit them all */
+} gq_sv_cliques;
+#ifdef __cplusplus
+static_assert(sizeof(gq_sv_stats) == 56, "gq_sv_stats layout");
+static_assert(sizeof(gq_sv_graph) == 48, "gq_sv_graph layout");
+static_assert(sizeof(gq_sv_cliques) == 48, "gq_sv_cliques layout");
+#endif
+/* pairs of a loaded file (after gq_bam_dev_load; a scan is not needed); parse_ms: device span  */
+gq_status gq_sv_pairs_from_bam(gq_bam_dev *b, gq_sv_pairs **out, float *parse_ms);
+/* pairs given as host arrays (already through the pairs stage's filter), strand: bit0 read on the
+ * reverse strand, bit1 mate on the reverse strand                                             */
+gq_status gq_sv_pairs_from_host(gq_ctx *ctx, int64_t n, const int32_t *contig, const int32_t *start,
+                                const int32_t *mate_contig, const int32_t *mate_start, const int32_t *tlen,
+                                const int32_t *len, const uint8_t *strand, gq_sv_pairs **out);
+int64_t gq_sv_pairs_count(const gq_sv_pairs *p);
+gq_status gq_sv_pairs_download(const gq_sv_pairs *p, int32_t *contig, int32_t *start, int32_t *mate_contig,
+                               int32_t *mate_start, int32_t *tlen, int32_t *len, uint8_t *strand);
+void gq_sv_pairs_free(gq_sv_pairs *p);
+/* stats, then the node set: the exceptional pairs in (contig, lo) order                        */
+gq_status gq_sv_stats_call(gq_sv_pairs *p, gq_sv_stats *out);
+/* the node set for a threshold of the caller's: in-range pairs with raw tlen > threshold       */
+gq_status gq_sv_select(gq_sv_pairs *p, int32_t threshold, int64_t *n_nodes);
+/* the node set: contig, lo, hi, len and the pair's index in the pairs SoA (null: not wanted)   */
+gq_status gq_sv_nodes_download(const gq_sv_pairs *p, int32_t *contig, int32_t *lo, int32_t *hi, int32_t *len,
+                               int64_t *pair);
+/* edges over the node set with N = max_normal.  GQ_E_CAPACITY when the edge list does not fit
+ * in device or host memory (nothing is truncated)                                             */
+gq_status gq_sv_graph_call(gq_sv_pairs *p, int32_t max_normal, gq_sv_graph **out);
+void gq_sv_free_graph(gq_sv_graph *g);
+/* host only: cliques of an edge list over nodes in (contig, lo) order (edges distinct, i < j)  */
+gq_status gq_sv_cliques_call(int64_t n_nodes, const int32_t *contig, const int32_t *lo, const int32_t *hi,
+                             const int32_t *len, int64_t n_edges, const int32_t *ei, const int32_t *ej,
+                             const int64_t *weight, int32_t max_normal, gq_sv_cliques **out);
+void gq_sv_free_cliques(gq_sv_cliques *c);
+/* stats + graph + cliques in one call; edge_ms / clique_ms (null: not wanted): the edge kernels'
+ * device span and the cliques' host time                                                      */
+gq_status gq_sv_call(gq_sv_pairs *p, gq_sv_stats *stats, gq_sv_cliques **out, float *edge_ms, float *clique_ms);
+
 #ifdef __cplusplus
 }
 #endif
