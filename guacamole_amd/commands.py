@@ -1315,11 +1315,71 @@ def structural_variant_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def realign_reads_main(argv: Sequence[str]) -> int:
+    """realign-reads: the reads with an insertion, deletion or soft clip aligned again against their
+    reference windows (AffineGapPenaltyAlignment.align, alignment/AffineGapPenaltyAlignment.scala:
+    20-46), one TSV line per selected read in resident order."""
+    import os
+    from . import align
+    from .bamdev import download
+    from .reference import ReferenceGenome
+    p = argparse.ArgumentParser(prog="realign-reads",
+                                description="affine-gap re-alignment of reads with indels or soft clips")
+    p.add_argument("--reads", required=True, help="Aligned reads")
+    p.add_argument("--reference-fasta", required=True, help="Local path to a reference FASTA file")
+    p.add_argument("--out", required=True, help="Output TSV path (must not exist)")
+    p.add_argument("--pad", type=int, default=32, help="Reference bases on each side of a read's window")
+    p.add_argument("--all-reads", action="store_true", help="Align every read, not only those with I, D or S ops")
+    p.add_argument("--mismatch-probability", type=float, default=None)
+    p.add_argument("--open-gap-probability", type=float, default=None)
+    p.add_argument("--close-gap-probability", type=float, default=None)
+    p.add_argument("--min-mapq", type=int, default=1, help="Rows only for reads of at least this mapping quality")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("realign-reads")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    clock = StageClock()
+    # the reads as stored: no MD tag is needed, so the load gets no reference (it would rebuild tags)
+    load_args = argparse.Namespace(reference_fasta="", recompute_md_tags=False, device=args.device)
+    ctx, (rs,) = load_product_reads(load_args, InputFilters.make(mapped=True, non_duplicate=True), args.reads)
+    if ctx is None:
+        ctx = native.Context(args.device)
+    dr = device_reads(ctx, rs)
+    clock.mark("load_reads")
+    dref = ctx.upload_reference(ReferenceGenome.load_fasta(args.reference_fasta).for_contigs(list(rs.contig_names)))
+    clock.mark("load_reference")
+    try:
+        res = align.realign_reads(ctx, dr, dref, pad=args.pad, all_reads=args.all_reads,
+                                  mismatch_probability=args.mismatch_probability,
+                                  open_gap_probability=args.open_gap_probability,
+                                  close_gap_probability=args.close_gap_probability)
+    finally:
+        dref.free()
+    clock.mark("align")
+    host = download(dr)
+    sel = res["read"]
+    contig = np.searchsorted(host["contig_read_begin"], sel, side="right") - 1
+    keep = host["mapq"][sel] >= args.min_mapq
+    co, nc = host["cigar_off"][sel], host["n_cigar"][sel]
+    lines = align.tsv_lines(res, [rs.contig_names[c] for c in contig], host["start"][sel],
+                            [align.to_cigar_string(host["cigar"][a:a + k]) for a, k in zip(co, nc)])
+    with open(args.out, "w") as fh:
+        fh.write(align.TSV_HEADER + "\n")
+        fh.writelines(l + "\n" for l, k in zip(lines, keep) if k)
+    clock.mark("write")
+    print("Aligned %d of %d reads (%d with N or P ops skipped); wrote %d rows." %
+          (res["n"], res["n_reads"], res["skipped"], int(keep.sum())), file=sys.stderr)
+    clock.report(selected=int(res["n"]), align_ms=res["ms"], kernel_ms=res["kernel_ms"])
+    return 0
+
+
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
-            "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main}
+            "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main,
+            "realign-reads": realign_reads_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -261,6 +261,23 @@ class gq_sv_cliques(C.Structure):
                 ("stop", C.POINTER(C.c_int64)), ("pairs", C.POINTER(C.c_int64)), ("wiggle", C.POINTER(C.c_int64))]
 
 
+class gq_align_params(C.Structure):
+    _fields_ = [("mismatch_probability", C.c_double), ("open_gap_probability", C.c_double),
+                ("close_gap_probability", C.c_double), ("reserved", C.c_double * 5)]
+
+
+class gq_alignments(C.Structure):
+    _fields_ = [("n", C.c_int64), ("ref_start", C.POINTER(C.c_int32)), ("ref_end", C.POINTER(C.c_int32)),
+                ("score", C.POINTER(C.c_double)), ("score_int", C.POINTER(C.c_int32)),
+                ("cigar_off", C.POINTER(C.c_int64)), ("cigar", C.POINTER(C.c_uint32)), ("ms", C.c_float),
+                ("kernel_ms", C.c_float), ("launches", C.c_int32), ("reserved", C.c_int32), ("block_", C.c_void_p)]
+
+
+class gq_align_reads_info(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_selected", C.c_int64), ("skipped", C.c_int64), ("select_ms", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -279,7 +296,9 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_free_pileup_counts", "gq_reads_rebuild_md", "gq_md_rebuild_spans", "gq_reads_missing_md",
             "gq_sv_pairs_from_bam", "gq_sv_pairs_from_host", "gq_sv_pairs_count", "gq_sv_pairs_download",
             "gq_sv_pairs_free", "gq_sv_stats_call", "gq_sv_select", "gq_sv_nodes_download", "gq_sv_graph_call",
-            "gq_sv_free_graph", "gq_sv_cliques_call", "gq_sv_free_cliques", "gq_sv_call")
+            "gq_sv_free_graph", "gq_sv_cliques_call", "gq_sv_free_cliques", "gq_sv_call",
+            "gq_align_default_params", "gq_align_penalties", "gq_align_limits", "gq_align_batch", "gq_align_host",
+            "gq_free_alignments", "gq_align_reads", "gq_align_free_index")
 
 
 def lib():
@@ -408,6 +427,23 @@ def lib():
         L.gq_sv_free_cliques.restype = None
         L.gq_sv_call.argtypes = [vp, C.POINTER(gq_sv_stats), C.POINTER(C.POINTER(gq_sv_cliques)),
                                  C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        for f in ("gq_align_penalties", "gq_align_batch", "gq_align_host", "gq_align_reads"):
+            getattr(L, f).restype = C.c_int
+        L.gq_align_default_params.argtypes = [C.POINTER(gq_align_params)]
+        L.gq_align_default_params.restype = None
+        L.gq_align_penalties.argtypes = [C.POINTER(gq_align_params), C.POINTER(C.c_double)]
+        L.gq_align_limits.argtypes = [C.POINTER(C.c_int32)]
+        L.gq_align_limits.restype = None
+        L.gq_align_host.argtypes = [C.c_int64] + [vp] * 6 + [C.POINTER(gq_align_params),
+                                                             C.POINTER(C.POINTER(gq_alignments))]
+        L.gq_align_batch.argtypes = [vp] + L.gq_align_host.argtypes
+        L.gq_free_alignments.argtypes = [C.POINTER(gq_alignments)]
+        L.gq_free_alignments.restype = None
+        L.gq_align_reads.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(gq_align_params),
+                                     C.POINTER(C.POINTER(gq_alignments)), C.POINTER(C.POINTER(C.c_int64)),
+                                     C.POINTER(C.POINTER(C.c_int32)), C.POINTER(gq_align_reads_info)]
+        L.gq_align_free_index.argtypes = [vp]
+        L.gq_align_free_index.restype = None
         _lib = L
     return _lib
 
@@ -427,6 +463,82 @@ def write_vcf_germline(path: str, header: str, calls: "GermlineCalls", contig_na
 def _check(rc: int) -> None:
     if rc != 0:
         raise GQError(rc, lib().gq_last_error().decode())
+
+
+# ---- affine-gap alignment (gq_align_*) ----
+E_ARG, E_CAPACITY = 7, 10
+
+
+def align_params(mismatch_probability: Optional[float] = None, open_gap_probability: Optional[float] = None,
+                 close_gap_probability: Optional[float] = None) -> gq_align_params:
+    """gq_align_params: the library's defaults (e^-4, e^-6, 1 - e^-1) where None."""
+    p = gq_align_params()
+    lib().gq_align_default_params(C.byref(p))
+    if mismatch_probability is not None:
+        p.mismatch_probability = float(mismatch_probability)
+    if open_gap_probability is not None:
+        p.open_gap_probability = float(open_gap_probability)
+    if close_gap_probability is not None:
+        p.close_gap_probability = float(close_gap_probability)
+    return p
+
+
+def align_penalties(**probabilities) -> np.ndarray:
+    """gq_align_penalties: the 32 step costs, [16 * (s == S) + 4 * last + next]."""
+    p = align_params(**probabilities)
+    t = np.zeros(32, np.float64)
+    _check(lib().gq_align_penalties(C.byref(p), t.ctypes.data_as(C.POINTER(C.c_double))))
+    return t
+
+
+def align_limits() -> Dict[str, int]:
+    """gq_align_limits: the device caps and the constants the traceback's placement depends on."""
+    v = (C.c_int32 * 8)()
+    lib().gq_align_limits(v)
+    return dict(max_s=v[0], max_r=v[1], lanes=v[2], max_rows=v[3], lds_bytes=v[4])
+
+
+def pack_pairs(sequences: Sequence[bytes], references: Sequence[bytes]):
+    """Host pools and offsets of (sequence, reference) pairs, as gq_align_batch takes them."""
+    if len(sequences) != len(references):
+        raise ValueError("%d sequences, %d references" % (len(sequences), len(references)))
+
+    def pool(items):
+        ln = np.array([len(x) for x in items], np.int32)
+        off = np.zeros(len(items), np.int64)
+        if len(items) > 1:
+            off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+        data = np.frombuffer(b"".join(bytes(x) for x in items) or b"\0", np.uint8)
+        return data, off, ln
+    return pool(sequences) + pool(references)
+
+
+def _alignments(out) -> Dict[str, object]:
+    """A gq_alignments block copied into numpy arrays (and freed)."""
+    try:
+        a = out.contents
+        n = int(a.n)
+        take = lambda p, k, dt: np.ctypeslib.as_array(p, (k,)).astype(dt, copy=True) if k else np.zeros(0, dt)
+        off = np.ctypeslib.as_array(a.cigar_off, (n + 1,)).astype(np.int64, copy=True)
+        return dict(n=n, ref_start=take(a.ref_start, n, np.int32), ref_end=take(a.ref_end, n, np.int32),
+                    score=take(a.score, n, np.float64), score_int=take(a.score_int, n, np.int32), cigar_off=off,
+                    cigar=take(a.cigar, int(off[n]), np.uint32), ms=float(a.ms), kernel_ms=float(a.kernel_ms),
+                    launches=int(a.launches))
+    finally:
+        lib().gq_free_alignments(out)
+
+
+def _pair_args(packed):
+    seq, so, sl, ref, ro, rl = packed
+    return [len(sl), seq.ctypes.data, so.ctypes.data, sl.ctypes.data, ref.ctypes.data, ro.ctypes.data, rl.ctypes.data]
+
+
+def align_host(packed, **probabilities) -> Dict[str, object]:
+    """gq_align_host over pack_pairs' arrays: the CPU twin of Context.align_batch."""
+    p = align_params(**probabilities)
+    out = C.POINTER(gq_alignments)()
+    _check(lib().gq_align_host(*_pair_args(packed), C.byref(p), C.byref(out)))
+    return _alignments(out)
 
 
 def _ptr(a) -> int:
@@ -538,6 +650,36 @@ class Context:
         _check(lib().gq_md_rebuild_spans(self.h, spans))
         return dict(rebuilt=int(info.rebuilt), md_events=int(info.md_events), ms=float(info.ms),
                     count_ms=float(spans[0]), scan_ms=float(spans[1]), fill_ms=float(spans[2]))
+
+    def align_batch(self, packed, **probabilities) -> Dict[str, object]:
+        """gq_align_batch over pack_pairs' arrays: ref_start, ref_end, score, score_int, cigar_off, cigar
+        (BAM words) per pair, the call's and the kernel's device spans (ms) and its launches."""
+        p = align_params(**probabilities)
+        out = C.POINTER(gq_alignments)()
+        _check(lib().gq_align_batch(self.h, *_pair_args(packed), C.byref(p), C.byref(out)))
+        return _alignments(out)
+
+    def align_reads(self, reads: "DeviceReads", dref: "DeviceReference", pad: int = 32, all_reads: bool = False,
+                    **probabilities) -> Dict[str, object]:
+        """gq_align_reads: the resident reads with an I, D or S op (all_reads: every read; never one
+        with an N or P op) against their windows of the resident reference.  align_batch's arrays,
+        plus read (resident indexes), lo (window starts), n_reads, skipped and select_ms."""
+        p = align_params(**probabilities)
+        out = C.POINTER(gq_alignments)()
+        idx, lo = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
+        info = gq_align_reads_info()
+        _check(lib().gq_align_reads(self.h, reads.h, dref.h, int(pad), int(bool(all_reads)), C.byref(p), C.byref(out),
+                                    C.byref(idx), C.byref(lo), C.byref(info)))
+        try:
+            k = int(info.n_selected)
+            res = dict(read=np.ctypeslib.as_array(idx, (k,)).astype(np.int64, copy=True) if k else np.zeros(0, np.int64),
+                       lo=np.ctypeslib.as_array(lo, (k,)).astype(np.int32, copy=True) if k else np.zeros(0, np.int32),
+                       n_reads=int(info.n_reads), skipped=int(info.skipped), select_ms=float(info.select_ms))
+        finally:
+            lib().gq_align_free_index(idx)
+            lib().gq_align_free_index(lo)
+        res.update(_alignments(out))
+        return res
 
     def missing_md(self, reads: "DeviceReads") -> int:
         """gq_reads_missing_md: reads of the resident set without MD events, counted on the device."""

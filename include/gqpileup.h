@@ -821,6 +821,91 @@ void gq_sv_free_cliques(gq_sv_cliques *c);
  * device span and the cliques' host time                                                      */
 gq_status gq_sv_call(gq_sv_pairs *p, gq_sv_stats *stats, gq_sv_cliques **out, float *edge_ms, float *clique_ms);
 
+/* Affine-gap alignment: AffineGapPenaltyAlignment.align (alignment/AffineGapPenaltyAlignment.scala:
+ * 20-141) and ReadAlignment.toCigar (alignment/ReadAlignment.scala:28-61), a batch of independent
+ * (sequence, reference) pairs.  Semi-global: the whole sequence against any stretch of the reference.
+ * Cell (s, r), s = 1..S, r = 0..R, keeps ONE path: its FP64 score and its last state; row 0 is score 0
+ * without a state.  Candidates in this order: Insertion from (s-1, r); Deletion from (s, r-1), r > 0;
+ * Match / Mismatch (raw bytes equal / not) from (s-1, r-1), r > 0; the first strictly smallest
+ * previous score + step cost wins.  The step cost depends on (last state, next state, s == S) only
+ * and comes from a table of 32 doubles built once on the host with the reference's term order:
+ *   table[16 * (s == S) + 4 * last + next], last: 0 none, 1 Insertion, 2 Deletion, 3 Match or
+ *   Mismatch; next: 0 Insertion, 1 Deletion, 2 Match, 3 Mismatch.
+ * ref_end = the first r with the strictly smallest score of row S, ref_start = the column where that
+ * path left row 0, score_int = (int)score as Double.toInt (truncated, saturating, NaN 0).  The CIGAR
+ * is the run-length encoded path in BAM words len << 4 | op with I 1, D 2, = 7, X 8.  An empty
+ * sequence gives no operations, score 0 and ref_start = ref_end = 0.
+ * Device caps: S <= 512, R <= 4096 (gq_align_limits); a pair beyond them is GQ_E_CAPACITY naming the
+ * pair, nothing is truncated and *out is not written.  The host twin has no caps.            */
+typedef struct {
+  double mismatch_probability;   /* e^-4     */
+  double open_gap_probability;   /* e^-6     */
+  double close_gap_probability;  /* 1 - e^-1 */
+  double reserved[5];            /* 0        */
+} gq_align_params;
+typedef struct {
+  int64_t n;
+  int32_t *ref_start, *ref_end;  /* [n] the aligned stretch [ref_start, ref_end) of the pair's reference */
+  double *score;                 /* [n]                                                        */
+  int32_t *score_int;            /* [n] ReadAlignment.alignmentScore                            */
+  int64_t *cigar_off;            /* [n + 1] into cigar                                          */
+  uint32_t *cigar;               /* BAM words                                                   */
+  float ms;                      /* device span of the call, copies included (0: host twin)     */
+  float kernel_ms;               /* ... of align_k alone, summed over the call's launches       */
+  int32_t launches;              /* align_k launches (scratch chunks)                           */
+  int32_t reserved;
+  void *block_;                  /* owner of the arrays above (gq_free_alignments)              */
+} gq_alignments;
+/* gq_align_reads: which reads were aligned, and against what */
+typedef struct {
+  int64_t n_reads;               /* reads of the resident set                                   */
+  int64_t n_selected;            /* aligned                                                     */
+  int64_t skipped;               /* reads with an N or P op: never selected                     */
+  float select_ms;               /* device span of selection + compaction                       */
+  int32_t reserved;
+} gq_align_reads_info;
+#ifdef __cplusplus
+static_assert(sizeof(gq_align_params) == 64, "gq_align_params layout");
+static_assert(sizeof(gq_alignments) == 80, "gq_alignments layout");
+static_assert(sizeof(gq_align_reads_info) == 32, "gq_align_reads_info layout");
+#endif
+/* The default probabilities. */
+void gq_align_default_params(gq_align_params *out);
+/* The step-cost table; GQ_E_ARG unless every probability lies strictly inside (0, 1). */
+gq_status gq_align_penalties(const gq_align_params *params, double table[32]);
+/* out[0..7]: max S, max R, lanes per pair (wave width), max rows per lane, bytes of LDS that hold
+ * a pair's traceback, 0, 0, 0.  Rows per lane of a pair = ceil(S / lanes), lanes used nl =
+ * ceil(S / rows per lane); its traceback takes nl * (R + nl) * (rows per lane <= 4 ? 1 : 2) bytes
+ * and lives in LDS when that fits, else in global scratch.                                   */
+void gq_align_limits(int32_t out[8]);
+/* Pair i: seq_pool[seq_off[i], + seq_len[i]) against ref_pool[ref_off[i], + ref_len[i]) (host
+ * arrays, copied to the device).  n == 0: GQ_OK, an empty block, no launch.  Scratch (global
+ * traceback and worst-case CIGAR space, (S + R) words a pair) is limited to a quarter of the free
+ * device memory, or to GQ_ALIGN_SCRATCH_BYTES when that environment variable is set (never less than
+ * one cap-sized pair needs): a batch that needs more runs as several launches over consecutive
+ * pairs, with the same result.                                                              */
+gq_status gq_align_batch(gq_ctx *ctx, int64_t n, const uint8_t *seq_pool, const int64_t *seq_off,
+                         const int32_t *seq_len, const uint8_t *ref_pool, const int64_t *ref_off,
+                         const int32_t *ref_len, const gq_align_params *params, gq_alignments **out);
+/* The same on the CPU (plain C++, no device, no caps): the twin the GPU results are compared with. */
+gq_status gq_align_host(int64_t n, const uint8_t *seq_pool, const int64_t *seq_off, const int32_t *seq_len,
+                        const uint8_t *ref_pool, const int64_t *ref_off, const int32_t *ref_len,
+                        const gq_align_params *params, gq_alignments **out);
+void gq_free_alignments(gq_alignments *a);
+/* Resident reads against windows of a resident reference; nothing is copied to the host but the
+ * selected reads' indexes and window bounds.  Selected: reads whose CIGAR holds an I, D or S op
+ * (every read with all_reads); a read with an N or P op is never selected and counted in
+ * info->skipped.  With lead / trail the summed lengths of the leading / trailing S ops (inside any
+ * H), end = the read's resident end, the window is [lo, hi) = [max(0, start - lead - pad),
+ * min(contig length, end + trail + pad)) and the sequence all stored bases of the read.  Selected
+ * reads keep resident order; (*read_index_out)[k] / (*lo_out)[k] (malloc'd, the caller frees) give
+ * pair k's resident index and window start.  GQ_E_ARG when a selected read lies on a contig the
+ * reference lacks, or `reference` does not cover the set's contigs.                          */
+gq_status gq_align_reads(gq_ctx *ctx, const gq_dev_reads *reads, const gq_reference *reference, int32_t pad,
+                         int32_t all_reads, const gq_align_params *params, gq_alignments **out,
+                         int64_t **read_index_out, int32_t **lo_out, gq_align_reads_info *info);
+void gq_align_free_index(void *p);
+
 #ifdef __cplusplus
 }
 #endif
