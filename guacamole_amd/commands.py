@@ -1374,12 +1374,69 @@ def realign_reads_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def assemble_windows_main(argv: Sequence[str]) -> int:
+    """assemble-windows: the de Bruijn graph of the reads' k-mers per window (assembly/
+    DeBruijnGraph.scala:271-294), its source-to-sink haplotypes and their alignment to the window,
+    one TSV line per haplotype."""
+    import os
+    from . import assemble
+    from .reference import ReferenceGenome
+    p = argparse.ArgumentParser(prog="assemble-windows", description="local assembly of the reads over windows")
+    p.add_argument("--reads", required=True, help="Aligned reads")
+    p.add_argument("--reference-fasta", required=True, help="Local path to a reference FASTA file")
+    p.add_argument("--loci", default="all", help="Loci to cut into windows (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--out", required=True, help="Output TSV path (must not exist)")
+    p.add_argument("--kmer-size", type=int, default=25)
+    p.add_argument("--min-occurrence", type=int, default=2, help="Occurrences a k-mer needs to be a node")
+    p.add_argument("--window-size", type=int, default=200)
+    p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
+    p.add_argument("--max-paths", type=int, default=10)
+    p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("assemble-windows")
+    if os.path.lexists(args.out):
+        raise FileExistsError("Output path %s already exists" % args.out)
+    clock = StageClock()
+    # the reads as stored, as realign-reads loads them
+    load_args = argparse.Namespace(reference_fasta="", recompute_md_tags=False, device=args.device)
+    ctx, (rs,) = load_product_reads(load_args, InputFilters.make(mapped=True, non_duplicate=True), args.reads)
+    if ctx is None:
+        ctx = native.Context(args.device)
+    dr = device_reads(ctx, rs)
+    clock.mark("load_reads")
+    names = list(rs.contig_names)
+    contigs = ReferenceGenome.load_fasta(args.reference_fasta).for_contigs(names)
+    dref = ctx.upload_reference(contigs)
+    clock.mark("load_reference")
+    loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
+    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                   args.window_step or None, args.kmer_size)
+    info: dict = {}
+    try:
+        rows = assemble.assemble_windows(ctx, dr, dref, windows, names, dict(zip(names, contigs)), k=args.kmer_size,
+                                         min_occurrence=args.min_occurrence, max_paths=args.max_paths,
+                                         min_mapq=args.min_mapq, info=info)
+    finally:
+        dref.free()
+    clock.mark("assemble")
+    with open(args.out, "w") as fh:
+        fh.write(assemble.TSV_HEADER + "\n")
+        fh.writelines(l + "\n" for l in assemble.tsv_lines(rows))
+    clock.mark("write")
+    print("Assembled %d windows into %d haplotypes; wrote %d rows." % (len(windows), info["n_haplotypes"], len(rows)),
+          file=sys.stderr)
+    clock.report(windows=len(windows), graphs_ms=info["ms"], paths_ms=info["paths_ms"], align_ms=info["align_ms"],
+                 global_windows=info["n_global"])
+    return 0
+
+
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
             "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main,
-            "realign-reads": realign_reads_main}
+            "realign-reads": realign_reads_main, "assemble-windows": assemble_windows_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -278,6 +278,32 @@ class gq_align_reads_info(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class gq_asm_params(C.Structure):
+    _fields_ = [("k", C.c_int32), ("min_occurrence", C.c_int32), ("max_paths", C.c_int32),
+                ("max_path_length", C.c_int32), ("max_steps", C.c_int64), ("min_mapq", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved", C.c_int64 * 4)]
+
+
+class gq_asm_graph_block(C.Structure):
+    _fields_ = [("n_windows", C.c_int64), ("n_nodes", C.c_int64), ("node_off", C.POINTER(C.c_int64)),
+                ("key_lo", C.POINTER(C.c_uint64)), ("key_hi", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)),
+                ("child_mask", C.POINTER(C.c_uint8)), ("parent_mask", C.POINTER(C.c_uint8)),
+                ("source", C.POINTER(C.c_int32)), ("sink", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_int32)),
+                ("n_reads", C.POINTER(C.c_int32)), ("win_len", C.POINTER(C.c_int32)),
+                ("n_instances", C.POINTER(C.c_int64)), ("k", C.c_int32), ("min_occurrence", C.c_int32),
+                ("ms", C.c_float), ("reads_ms", C.c_float), ("count_ms", C.c_float), ("edges_ms", C.c_float),
+                ("launches", C.c_int32), ("n_global", C.c_int32), ("block_", C.c_void_p)]
+
+
+class gq_asm_path_block(C.Structure):
+    _fields_ = [("n_windows", C.c_int64), ("n_haplotypes", C.c_int64), ("n_unitigs", C.c_int64),
+                ("hap_off", C.POINTER(C.c_int64)), ("hap_seq_off", C.POINTER(C.c_int64)),
+                ("bases", C.POINTER(C.c_uint8)), ("support", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_int32)),
+                ("steps", C.POINTER(C.c_int64)), ("unitig_off", C.POINTER(C.c_int64)),
+                ("unitig_seq_off", C.POINTER(C.c_int64)), ("unitig_bases", C.POINTER(C.c_uint8)), ("ms", C.c_float),
+                ("reserved", C.c_int32), ("block_", C.c_void_p)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -298,7 +324,9 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_sv_pairs_free", "gq_sv_stats_call", "gq_sv_select", "gq_sv_nodes_download", "gq_sv_graph_call",
             "gq_sv_free_graph", "gq_sv_cliques_call", "gq_sv_free_cliques", "gq_sv_call",
             "gq_align_default_params", "gq_align_penalties", "gq_align_limits", "gq_align_batch", "gq_align_host",
-            "gq_free_alignments", "gq_align_reads", "gq_align_free_index")
+            "gq_free_alignments", "gq_align_reads", "gq_align_free_index",
+            "gq_asm_default_params", "gq_asm_limits", "gq_asm_graphs", "gq_asm_graphs_host", "gq_asm_free_graphs",
+            "gq_asm_paths", "gq_asm_free_paths")
 
 
 def lib():
@@ -444,6 +472,22 @@ def lib():
                                      C.POINTER(C.POINTER(C.c_int32)), C.POINTER(gq_align_reads_info)]
         L.gq_align_free_index.argtypes = [vp]
         L.gq_align_free_index.restype = None
+        for f in ("gq_asm_graphs", "gq_asm_graphs_host", "gq_asm_paths"):
+            getattr(L, f).restype = C.c_int
+        L.gq_asm_default_params.argtypes = [C.POINTER(gq_asm_params)]
+        L.gq_asm_default_params.restype = None
+        L.gq_asm_limits.argtypes = [C.POINTER(C.c_int32)]
+        L.gq_asm_limits.restype = None
+        L.gq_asm_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.POINTER(gq_asm_params),
+                                    C.POINTER(C.POINTER(gq_asm_graph_block))]
+        L.gq_asm_graphs_host.argtypes = [C.c_int64] + [vp] * 8 + [C.POINTER(gq_asm_params), C.c_int32,
+                                                                  C.POINTER(C.POINTER(gq_asm_graph_block))]
+        L.gq_asm_free_graphs.argtypes = [C.POINTER(gq_asm_graph_block)]
+        L.gq_asm_free_graphs.restype = None
+        L.gq_asm_paths.argtypes = [C.POINTER(gq_asm_graph_block), C.POINTER(gq_asm_params),
+                                   C.POINTER(C.POINTER(gq_asm_path_block))]
+        L.gq_asm_free_paths.argtypes = [C.POINTER(gq_asm_path_block)]
+        L.gq_asm_free_paths.restype = None
         _lib = L
     return _lib
 
@@ -539,6 +583,122 @@ def align_host(packed, **probabilities) -> Dict[str, object]:
     out = C.POINTER(gq_alignments)()
     _check(lib().gq_align_host(*_pair_args(packed), C.byref(p), C.byref(out)))
     return _alignments(out)
+
+
+# ---- local assembly (gq_asm_*) ----
+ASM_STATUS = {0: "OK", 1: "SHORT", 2: "REF_N", 3: "NO_SOURCE", 4: "NO_SINK"}
+ASM_CAPS = ((16, "PATHS_CAPPED"), (32, "STEPS_CAPPED"), (64, "LENGTH_CAPPED"))
+
+
+def asm_status_name(status: int) -> str:
+    """A gq_asm_paths status as text: the graph's status, then the caps its search met."""
+    return "|".join([ASM_STATUS[status & 15]] + [n for b, n in ASM_CAPS if status & b])
+
+
+def asm_params(k: Optional[int] = None, min_occurrence: Optional[int] = None, max_paths: Optional[int] = None,
+               max_path_length: Optional[int] = None, max_steps: Optional[int] = None,
+               min_mapq: Optional[int] = None) -> gq_asm_params:
+    """gq_asm_params: the library's defaults (k 25, 1, 10, window length - k + 65, 1,000,000) where None."""
+    p = gq_asm_params()
+    lib().gq_asm_default_params(C.byref(p))
+    for name, v in (("k", k), ("min_occurrence", min_occurrence), ("max_paths", max_paths),
+                    ("max_path_length", max_path_length), ("max_steps", max_steps), ("min_mapq", min_mapq)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def asm_limits() -> Dict[str, int]:
+    """gq_asm_limits: the k range and the shape of the device table."""
+    v = (C.c_int32 * 8)()
+    lib().gq_asm_limits(v)
+    return dict(min_k=v[0], max_k=v[1], word_bases=v[2], lds_slots=v[3], lds_slots_max=v[4], threads=v[5],
+                lds_bytes=v[6])
+
+
+GRAPH_ARRAYS = ("node_off", "key_lo", "key_hi", "count", "child_mask", "parent_mask", "source", "sink", "status",
+                "n_reads", "win_len", "n_instances")
+
+
+class AsmGraphs:
+    """A gq_asm_graph_block (the device's or the twin's): `a` holds numpy copies of its arrays, the
+    block itself lives until this object goes, for paths()."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+        g = ptr.contents
+        w, n = int(g.n_windows), int(g.n_nodes)
+        take = lambda p, k: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, p._type_)
+        self.n_windows, self.n_nodes, self.k, self.min_occurrence = w, n, int(g.k), int(g.min_occurrence)
+        self.a = {name: take(getattr(g, name), w + 1 if name == "node_off" else n if name in GRAPH_ARRAYS[1:6] else w)
+                  for name in GRAPH_ARRAYS}
+        self.info = dict(ms=float(g.ms), reads_ms=float(g.reads_ms), count_ms=float(g.count_ms),
+                         edges_ms=float(g.edges_ms), launches=int(g.launches), n_global=int(g.n_global))
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            lib().gq_asm_free_graphs(self.ptr)
+            self.ptr = None
+
+    def paths(self, max_paths: Optional[int] = None, max_path_length: Optional[int] = None,
+              max_steps: Optional[int] = None) -> Dict[str, object]:
+        """gq_asm_paths: haplotypes (offsets, bases, support), status and steps per window, unitigs."""
+        p = asm_params(self.k, self.min_occurrence, max_paths, max_path_length, max_steps)
+        out = C.POINTER(gq_asm_path_block)()
+        _check(lib().gq_asm_paths(self.ptr, C.byref(p), C.byref(out)))
+        try:
+            b = out.contents
+            w, nh, nu = int(b.n_windows), int(b.n_haplotypes), int(b.n_unitigs)
+            take = lambda p, k: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, p._type_)
+            so, uo = take(b.hap_seq_off, nh + 1), take(b.unitig_seq_off, nu + 1)
+            return dict(hap_off=take(b.hap_off, w + 1), hap_seq_off=so, bases=take(b.bases, int(so[nh])).tobytes(),
+                        support=take(b.support, nh), status=take(b.status, w), steps=take(b.steps, w),
+                        unitig_off=take(b.unitig_off, w + 1), unitig_seq_off=uo,
+                        unitig_bases=take(b.unitig_bases, int(uo[nu])).tobytes(), ms=float(b.ms))
+        finally:
+            lib().gq_asm_free_paths(out)
+
+
+def asm_graphs_host(sequences: Sequence[bytes], window_reads: Sequence[Sequence[int]],
+                    window_refs: Sequence[Optional[bytes]], window_lens: Optional[Sequence[int]] = None,
+                    threads: int = 1, **params) -> AsmGraphs:
+    """gq_asm_graphs_host: window w has the reads window_reads[w] (indexes into `sequences`) and the
+    reference bytes window_refs[w] (None: no reference, its length then from window_lens)."""
+    return asm_graphs_host_packed(asm_pack_host(sequences, window_reads, window_refs, window_lens), threads, **params)
+
+
+def asm_pack_host(sequences: Sequence[bytes], window_reads: Sequence[Sequence[int]],
+                  window_refs: Sequence[Optional[bytes]], window_lens: Optional[Sequence[int]] = None):
+    """asm_graphs_host's arguments as gq_asm_graphs_host's arrays, for asm_graphs_host_packed."""
+    seq, so, sl = pack_pairs(sequences, sequences)[:3]
+    cnt = np.array([len(x) for x in window_reads], np.int64)
+    roff = np.zeros(len(window_reads) + 1, np.int64)
+    roff[1:] = np.cumsum(cnt)
+    reads = np.array([r for x in window_reads for r in x] or [0], np.int64)
+    refs = [b"" if x is None else bytes(x) for x in window_refs]
+    wl = np.array([len(r) if x is not None else int(window_lens[i])
+                   for i, (x, r) in enumerate(zip(window_refs, refs))] or [0], np.int32)
+    ro = np.zeros(max(1, len(refs)), np.int64)
+    at = 0
+    for i, (x, r) in enumerate(zip(window_refs, refs)):
+        ro[i] = -1 if x is None else at
+        at += len(r)
+    pool = np.frombuffer(b"".join(refs) or b"\0", np.uint8)
+    return (len(window_reads), seq, so, sl, roff, reads, pool, ro, wl)
+
+
+def asm_graphs_host_call(packed, threads: int = 1, **params):
+    """The gq_asm_graphs_host call alone over asm_pack_host's arrays: the block's pointer (AsmGraphs
+    takes it over)."""
+    p = asm_params(**params)
+    out = C.POINTER(gq_asm_graph_block)()
+    _check(lib().gq_asm_graphs_host(packed[0], *[a.ctypes.data for a in packed[1:]], C.byref(p), int(threads),
+                                    C.byref(out)))
+    return out
+
+
+def asm_graphs_host_packed(packed, threads: int = 1, **params) -> AsmGraphs:
+    return AsmGraphs(asm_graphs_host_call(packed, threads, **params))
 
 
 def _ptr(a) -> int:
@@ -658,6 +818,16 @@ class Context:
         out = C.POINTER(gq_alignments)()
         _check(lib().gq_align_batch(self.h, *_pair_args(packed), C.byref(p), C.byref(out)))
         return _alignments(out)
+
+    def asm_graphs(self, reads: "DeviceReads", dref: "DeviceReference", contig, start, end, **params) -> AsmGraphs:
+        """gq_asm_graphs: the de Bruijn graphs of the windows (contig index, [start, end)) of the
+        resident reads, with source and sink from the resident reference."""
+        c, s, e = (np.ascontiguousarray(x, np.int32) for x in (contig, start, end))
+        p = asm_params(**params)
+        out = C.POINTER(gq_asm_graph_block)()
+        _check(lib().gq_asm_graphs(self.h, reads.h, dref.h, len(c), c.ctypes.data, s.ctypes.data, e.ctypes.data,
+                                   C.byref(p), C.byref(out)))
+        return AsmGraphs(out)
 
     def align_reads(self, reads: "DeviceReads", dref: "DeviceReference", pad: int = 32, all_reads: bool = False,
                     **probabilities) -> Dict[str, object]:

@@ -906,6 +906,108 @@ gq_status gq_align_reads(gq_ctx *ctx, const gq_dev_reads *reads, const gq_refere
                          int64_t **read_index_out, int32_t **lo_out, gq_align_reads_info *info);
 void gq_align_free_index(void *p);
 
+/* Local assembly over windows: assembly/DeBruijnGraph.scala restated (DESIGN.md "Local assembly").
+ * A window is (contig, [start, end)).  Its reads: every resident read whose [start, end) overlaps it,
+ * all stored bases (soft clips included), unless a byte is not one of upper-case A C G T or the read
+ * is shorter than k.  count(x) = occurrences of k-mer x over those reads; x is a node iff count >=
+ * min_occurrence.  A k-mer is packed 2 bits a base (A 0, C 1, G 2, T 3), first base most significant:
+ * key_lo holds its last min(k, 31) bases, key_hi the k - 31 before them (0 for k <= 31).  A window's
+ * nodes stand sorted by k-mer, i.e. by (key_hi, key_lo).  child_mask bit b: the node's k - 1 last
+ * bases followed by base b is a node; parent_mask bit b: base b followed by its k - 1 first bases is.
+ * source / sink: the node index (within the window) of the first / last k bytes of the window's
+ * reference, -1 when it is no node.  status, the first that holds: GQ_ASM_SHORT (window shorter than
+ * k), GQ_ASM_REF_N (contig absent from the reference, window past its end, or a byte of the source
+ * or sink outside A C G T), GQ_ASM_NO_SOURCE, GQ_ASM_NO_SINK, else GQ_ASM_OK.  The graph is built
+ * whatever the status.                                                                        */
+enum {
+  GQ_ASM_OK = 0, GQ_ASM_SHORT = 1, GQ_ASM_REF_N = 2, GQ_ASM_NO_SOURCE = 3, GQ_ASM_NO_SINK = 4,
+  /* gq_asm_paths ORs these into an OK window's status when its search met a cap */
+  GQ_ASM_PATHS_CAPPED = 16, GQ_ASM_STEPS_CAPPED = 32, GQ_ASM_LENGTH_CAPPED = 64
+};
+typedef struct {
+  int32_t k;                /* 2 .. 62                                                          */
+  int32_t min_occurrence;   /* >= 1 (1)                                                         */
+  int32_t max_paths;        /* >= 1 (10)                                                        */
+  int32_t max_path_length;  /* k-mers of a path; 0: window length - k + 1 + 64                  */
+  int64_t max_steps;        /* node visits of a window's search (1,000,000)                     */
+  int32_t min_mapq;         /* gq_asm_graphs: only reads of at least this mapping quality (0)   */
+  int32_t reserved0;        /* 0                                                                */
+  int64_t reserved[4];      /* 0                                                                */
+} gq_asm_params;
+typedef struct {
+  int64_t n_windows, n_nodes;
+  int64_t *node_off;                    /* [n_windows + 1] into the node arrays                  */
+  uint64_t *key_lo, *key_hi;            /* [n_nodes]                                             */
+  int32_t *count;                       /* [n_nodes]                                             */
+  uint8_t *child_mask, *parent_mask;    /* [n_nodes]                                             */
+  int32_t *source, *sink, *status;      /* [n_windows]                                           */
+  int32_t *n_reads;                     /* [n_windows] reads that contributed                    */
+  int32_t *win_len;                     /* [n_windows] end - start                               */
+  int64_t *n_instances;                 /* [n_windows] k-mer occurrences counted                 */
+  int32_t k, min_occurrence;
+  float ms;                             /* device span of the call, copies included (0: twin)    */
+  float reads_ms;                       /* ... of finding the windows' reads                     */
+  float count_ms, edges_ms;             /* ... of asm_window_k, split by its own clock readings into
+                                           counting and prune / order / edges                    */
+  int32_t launches;                     /* asm_window_k launches                                 */
+  int32_t n_global;                     /* windows counted over a table in global scratch        */
+  void *block_;                         /* owner of the arrays above (gq_asm_free_graphs)        */
+} gq_asm_graph_block;
+typedef struct {
+  int64_t n_windows, n_haplotypes, n_unitigs;
+  int64_t *hap_off;         /* [n_windows + 1] a window's haplotypes, in discovery order          */
+  int64_t *hap_seq_off;     /* [n_haplotypes + 1] into bases                                     */
+  uint8_t *bases;           /* mergeKmers of each path                                           */
+  int32_t *support;         /* [n_haplotypes] smallest count along the path                      */
+  int32_t *status;          /* [n_windows] the graph's status | GQ_ASM_*_CAPPED                  */
+  int64_t *steps;           /* [n_windows] node visits of the search                             */
+  int64_t *unitig_off;      /* [n_windows + 1] a window's unitigs, by first k-mer                */
+  int64_t *unitig_seq_off;  /* [n_unitigs + 1] into unitig_bases                                 */
+  uint8_t *unitig_bases;
+  float ms;                 /* host time of the call                                             */
+  int32_t reserved;
+  void *block_;
+} gq_asm_path_block;
+#ifdef __cplusplus
+static_assert(sizeof(gq_asm_params) == 64, "gq_asm_params layout");
+static_assert(sizeof(gq_asm_graph_block) == 152, "gq_asm_graph_block layout");
+static_assert(sizeof(gq_asm_path_block) == 112, "gq_asm_path_block layout");
+#endif
+void gq_asm_default_params(gq_asm_params *out);
+/* out[0..7]: min k, max k, bases per key word, LDS table slots in use (GQ_ASM_LDS_SLOTS applied),
+ * LDS table slots compiled in, threads per window, LDS bytes per workgroup, 0                 */
+void gq_asm_limits(int32_t out[8]);
+/* The graphs of n_windows windows of a resident read set; contig indexes the set's contig list.
+ * GQ_E_ARG for k outside 2 .. 62, a contig outside the list, start < 0 or end < start.  n_windows
+ * == 0: GQ_OK, an empty block, no launch.  A window is counted over a hash table in LDS; one whose
+ * distinct k-mers do not fit is counted again by the same code over a table in global scratch sized
+ * from its instance count.  GQ_ASM_LDS_SLOTS (environment, rounded down to a power of two, at least
+ * 2) caps the LDS table.  Scratch is limited to a quarter of the free device memory, or to
+ * GQ_ASM_SCRATCH_BYTES when set (never less than one window needs): a batch that needs more runs as
+ * several launches over consecutive windows, with the same result.                             */
+gq_status gq_asm_graphs(gq_ctx *ctx, const gq_dev_reads *reads, const gq_reference *reference, int64_t n_windows,
+                        const int32_t *contig, const int32_t *start, const int32_t *end,
+                        const gq_asm_params *params, gq_asm_graph_block **out);
+/* The same block on the CPU (plain C++, no device), bit for bit.  Read r = seq_pool[seq_off[r], +
+ * seq_len[r]); window w lists its overlapping reads win_reads[win_read_off[w] .. win_read_off[w + 1])
+ * and has the win_len[w] reference bytes at ref_pool + ref_off[w] (ref_off[w] < 0: none, REF_N).
+ * threads: worker threads over the windows (<= 1: the calling thread).                          */
+gq_status gq_asm_graphs_host(int64_t n_windows, const uint8_t *seq_pool, const int64_t *seq_off,
+                             const int32_t *seq_len, const int64_t *win_read_off, const int64_t *win_reads,
+                             const uint8_t *ref_pool, const int64_t *ref_off, const int32_t *win_len,
+                             const gq_asm_params *params, int32_t threads, gq_asm_graph_block **out);
+void gq_asm_free_graphs(gq_asm_graph_block *g);
+/* Host only: haplotypes and unitigs of a graph block (either producer's).  Haplotypes of an OK
+ * window: every simple path source .. sink, depth first, children in A C G T order, a node barred
+ * only while on the current path; a path that reaches the sink ends there.  Entering a node is a
+ * step.  A child that would make the path longer than max_path_length is not entered
+ * (LENGTH_CAPPED); the search stops when a step beyond max_steps (STEPS_CAPPED) or a path beyond
+ * max_paths (PATHS_CAPPED) is due.  Unitigs of every window: the maximal paths whose steps x -> y
+ * have y the only child of x and x the only parent of y (x != y), sorted by first k-mer; an
+ * unbranched cycle starts at its smallest k-mer.  params->k and min_occurrence are the block's. */
+gq_status gq_asm_paths(const gq_asm_graph_block *graphs, const gq_asm_params *params, gq_asm_path_block **out);
+void gq_asm_free_paths(gq_asm_path_block *p);
+
 #ifdef __cplusplus
 }
 #endif
