@@ -144,6 +144,66 @@ def test_twin_random_windows():
         A.check_twin(windows, k, 2, threads=4, max_paths=3, max_steps=200)
 
 
+# ---- the builders of test_gpu_assembly_limits.py: their preconditions, and the twin at their shapes ----
+def test_twin_table_size_windows():
+    """The windows around the device table's real size hold exactly the intended k-mers, before and
+    after pruning.  (Restated whole, uncapped: a window is one chain, which the restatement's search
+    walks once.)"""
+    k = 25
+    lim = native.asm_limits()
+    threads, slots = lim["threads"], lim["lds_slots_max"]
+    windows, distinct, twice = A.table_size_windows(k)
+    assert distinct == [threads - 1, threads, threads + 1, 2 * threads + 1, slots - 1, slots, slots + 1, slots, 3000, 40]
+    assert twice == distinct[:7] + [threads + 1, threads + 1, 40]
+    for min_occurrence, want in ((1, distinct), (2, twice)):
+        got = A.check_twin(windows, k, min_occurrence)
+        assert [len(w["nodes"]) for w in got] == want
+        assert [w["status"] for w in got] == [R.OK] * len(windows)
+    assert [len(w["haplotypes"]) for w in got] == [1] * 7 + [0, 0, 1]  # the single reads cut the part windows' chain
+
+
+@pytest.mark.parametrize("k", [32, 33, 47, 62])
+def test_twin_shared_word_windows(k):
+    windows = A.shared_word_windows(k)
+    word = native.asm_limits()["word_bases"]
+    g = A.host_graphs(windows, k)
+    assert A.shared_word_pairs(g, 0, "key_lo", "key_hi") >= 3 * min(12, k - word)
+    assert A.shared_word_pairs(g, 1, "key_hi", "key_lo") >= 3 * min(12, k - word)
+    n2 = int(g.a["node_off"][3] - g.a["node_off"][2])  # the packed window: a power of two, all in groups of four
+    assert n2 == 256 and A.shared_word_pairs(g, 2, "key_lo", "key_hi") == 6 * n2 // 4
+    assert all(n2 // 2 < int(d) <= n2 for d in np.diff(g.a["node_off"]))
+    counts = set(int(x) for x in g.a["count"])
+    assert all(c % 64 == 0 for c in counts) and min(counts) == 64 and max(counts) >= 128  # 65 splits them
+    whole, pruned = A.check_twin(windows, k, 1), A.check_twin(windows, k, 65)
+    for w, p in zip(whole, pruned):
+        assert 0 < len(p["nodes"]) < len(w["nodes"]) and w["status"] == R.OK
+
+
+def test_twin_front_end_case():
+    k, min_mapq = 25, 20
+    case = A.front_end_case(k, min_mapq)
+    reads, windows = case["reads"], case["windows"]
+    assert len(windows) >= 600 and windows != sorted(windows) and len(set(windows)) < len(windows)
+    assert sorted(set(r["contig"] for r in reads)) == [1, 3]
+    lists = {w: A.window_reads(reads, w, k, min_mapq) for w in set(windows)}
+    assert lists[case["far"]] == [case["long"]] and case["long"] == 0  # found only through pmax_end
+    assert sum(1 for r in reads if r["contig"] == 1 and r["start"] + A.cigar_span(r["cigar"]) <= case["far"][1]) > 100
+    assert lists[case["deleted_only"]] == [case["deleted"]]
+    assert case["deleted_only"][1] > reads[case["deleted"]]["start"] + len(reads[case["deleted"]]["seq"])
+    assert lists[case["clipped_only"]] == [] and lists[case["empty"]] == [] and lists[case["past"]] == []
+    assert reads[case["clipped"]]["start"] == case["clipped_only"][2]
+    assert case["long"] in lists[case["unit"]]
+    assert all(lists[w] == [] for w in windows if w[0] in (0, 2, 4))
+    assert sum(len(lists[w]) for w in windows) > 10 * 256
+    taken = set(i for w in windows for i in lists[w])
+    left = [r for i, r in enumerate(reads) if i not in taken]  # the short one, the one with an N, those below min_mapq
+    assert sorted((len(r["seq"]), r["mapq"]) for r in left) == [(k - 1, 30)] + [(40, min_mapq - 1)] * 3 + [(40, 30)]
+    got = A.check_twin(A.front_end_windows(case, k, min_mapq), k)
+    assert [w["n_reads"] for w in got] == [len(lists[w]) for w in windows]
+    g = A.front_end_twin(case, k, min_mapq)
+    assert [int(x) for x in g.a["n_reads"]] == [len(lists[w]) for w in windows]
+
+
 def test_cut_windows():
     assert assemble.cut_windows([("c", 0, 450)], 200, None, 25) == [("c", 0, 200), ("c", 200, 400), ("c", 400, 450)]
     assert assemble.cut_windows([("c", 0, 420)], 200, None, 25) == [("c", 0, 200), ("c", 200, 400)]
