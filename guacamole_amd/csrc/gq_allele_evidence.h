@@ -1,10 +1,12 @@
 // gq_allele_evidence.h — allele-evidence (gq_allele_evidence): AlleleEvidence.apply
 // (variants/AlleleEvidence.scala:58-101) for every distinct allele of every sample's pileup.
 // Included by gq_somatic.hip inside its anonymous namespace, after the caller's device helpers
-// (make_cover, pileup_ref, gather_sample, pile_desc, DeepSel, GsMem).
+// (make_cover, pileup_ref, gather_sample, pile_desc, DeepSel, GsMem) and gq_locus_driver.h (the
+// list kernel, the per-locus prologue, the host loop).
 //
 // Two kernels:
-//   allele_evidence_list<T>   one workgroup per tile of T loci at a time: the LDS histogram of the
+//   allele_evidence_list<T>   (gq_locus_driver.h)
+//                               one workgroup per tile of T loci at a time: the LDS histogram of the
 //                             reads the mapq filter keeps (the germline sink), the reference-base
 //                             bits of the reads it drops in a second histogram (the pileup's
 //                             reference base is the unfiltered pileup's), and per locus "the
@@ -27,8 +29,6 @@
 //                             instantiation (per-wave HBM scratch, 1024 alleles).
 #pragma once
 
-constexpr int kAeT = 512;  // loci per list tile
-
 struct AeRec {  // one row
   uint64_t key;  // locus ordinal << 20 | sample << 12 | rank of the allele among the sample's by (ref, alt)
   int32_t contig, pos;
@@ -38,87 +38,6 @@ struct AeRec {  // one row
   gq_evidence ev;
 };
 static_assert(sizeof(AeRec) == 96, "AeRec layout");
-
-// items[k] = a locus to process; flags bit0: listed unconditionally (a tile whose read window could
-// overflow the 16-bit counters): the call kernel counts the visit and applies variants_only itself.
-template <int T>
-__global__ __launch_bounds__(kBlock) void allele_evidence_list(const Tile *__restrict__ tiles, int64_t n_tiles, DevReads R,
-                                                               int min_mapq, int variants_only,
-                                                               ComplexItem *__restrict__ items,
-                                                               unsigned long long item_cap, Counters *ctr) {
-  constexpr int S = T + 2 * kGuard;
-  constexpr int KPT = T / kBlock;
-  __shared__ __attribute__((aligned(16))) uint32_t cnt[W_N * S];  // the reads the filter keeps
-  __shared__ __attribute__((aligned(16))) uint32_t low[W_N * S];  // the reads it drops (reference-base bits)
-  unsigned visited = 0;
-  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const Tile tt = tiles[t];
-    const int32_t L0 = tt.L0, L1 = tt.L1;
-    const int nloci = L1 - L0;
-    if ((tt.re - tt.rb) >= 65535) {
-#pragma unroll
-      for (int k = 0; k < KPT; ++k) {
-        const int i = threadIdx.x + k * kBlock;
-        const unsigned long long b = wave_reserve(&ctr->n_complex, i < nloci ? 1u : 0u);
-        if (i < nloci && b < item_cap) items[b] = ComplexItem{(int32_t)t, L0 + i, 1};
-      }
-      continue;
-    }
-    uint4 *c4 = reinterpret_cast<uint4 *>(cnt), *l4 = reinterpret_cast<uint4 *>(low);
-    __syncthreads();  // the previous tile's readers are done
-    for (int i = threadIdx.x; i < W_N * S / 4; i += blockDim.x) c4[i] = l4[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-    {
-      GermSink<T, 0> keep{cnt, L0, &ctr->err, &ctr->err_pos}, drop{low, L0, &ctr->err, &ctr->err_pos};
-      for (int64_t r = tt.rb + threadIdx.x; r < tt.re; r += blockDim.x) {
-        if (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq) walk_read_lane(R, r, L0, L1, keep);
-        else walk_read_lane(R, r, L0, L1, drop);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) {
-      const int i = threadIdx.x + k * kBlock;
-      bool q = false;
-      if (i < nloci) {
-        const uint32_t wac = cnt[W_AC * S + kGuard + i], wtg = cnt[W_TG * S + kGuard + i],
-                       wox = cnt[W_OX * S + kGuard + i], wnn = cnt[W_NN * S + kGuard + i];
-        const uint32_t cA = wac & 0xFFFFu, cC = wac >> 16, cT = wtg & 0xFFFFu, cG = wtg >> 16, cN = wnn >> 16;
-        const uint32_t cx = (wox & 0xFFFFu) + (wox >> 16);
-        const uint32_t depth = cA + cC + cT + cG + cN + cx;
-        if (depth > 0) {
-          ++visited;
-          // the standard MD-derived reference bases of every covering read, kept or dropped
-          uint32_t mask = (wnn | low[W_NN * S + kGuard + i]) & 0xFu;
-          const uint32_t eac = cnt[W_EAC * S + kGuard + i], etg = cnt[W_ETG * S + kGuard + i];
-          if (cA > (eac & 0xFFFFu)) mask |= 1u;
-          if (cC > (eac >> 16)) mask |= 2u;
-          if (cT > (etg & 0xFFFFu)) mask |= 4u;
-          if (cG > (etg >> 16)) mask |= 8u;
-          const uint32_t lac = low[W_AC * S + kGuard + i], ltg = low[W_TG * S + kGuard + i],
-                         lea = low[W_EAC * S + kGuard + i], let = low[W_ETG * S + kGuard + i];
-          if ((lac & 0xFFFFu) > (lea & 0xFFFFu)) mask |= 1u;
-          if ((lac >> 16) > (lea >> 16)) mask |= 2u;
-          if ((ltg & 0xFFFFu) > (let & 0xFFFFu)) mask |= 4u;
-          if ((ltg >> 16) > (let >> 16)) mask |= 8u;
-          const int rc = mask ? (__ffs((int)mask) - 1) : 4;
-          const uint32_t c_ref = rc == 0 ? cA : rc == 1 ? cC : rc == 2 ? cT : rc == 3 ? cG : cN;
-          // heap order decides the reference base (the call kernel lists the locus, and applies
-          // variants_only once the base is known), or a non-Match element
-          q = !variants_only || __popc(mask) > 1 || cx > 0 || depth > c_ref;
-        }
-      }
-      const unsigned long long b = wave_reserve(&ctr->n_complex, q ? 1u : 0u);
-      if (q && b < item_cap) items[b] = ComplexItem{(int32_t)t, L0 + i, 0};
-    }
-  }
-  __shared__ unsigned red;
-  if (threadIdx.x == 0) red = 0;
-  __syncthreads();
-  if (visited) atomicAdd(&red, visited);
-  __syncthreads();
-  if (threadIdx.x == 0 && red) atomicAdd(&ctr->spread[0][blockIdx.x & (kSpread - 1)], (unsigned long long)red);
-}
 
 // k-th smallest (0-based) of field `field` (0 mapq, 1 quality (signed), 2 mismatches) of the n
 // packed words at ev, by rank counting, lane-parallel over the elements (allele_evidence's scheme).
@@ -160,7 +79,6 @@ __device__ __forceinline__ double ae_entry_f64(const double (&a)[NS], int j) {
   return v;
 }
 
-// Hand-over entries (dd.out / dd.sel): list position << 9 | visit counted << 8 | first sample left.
 template <bool DEEP>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1 : 2))) void allele_evidence_call(
     const Tile *__restrict__ tiles, const ComplexItem *__restrict__ items, int64_t n_items, DevReads R,
@@ -175,77 +93,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   const int64_t gwave = wave_id();
   const int64_t nwaves_total = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  GsMem m;
-  if constexpr (DEEP) {
-    m = gs_deep_mem(dd.scratch + (size_t)gwave * gs_wave_bytes(dd.scap, dd.maxG), dd.scap, dd.maxG);
-  } else {
-    m = GsMem{cover_a[wv], cover_s[wv], ev_lds[wv], nullptr, nullptr, nullptr, kCover, kEvCap / 2, 0};
-  }
+  const GsMem m = locus_mem<DEEP>(dd, cover_a[DEEP ? 0 : wv], cover_s[DEEP ? 0 : wv], ev_lds[DEEP ? 0 : wv], kEvCap / 2, 0);
   const uint32_t evcap = (uint32_t)(DEEP ? 2 * m.cap : kEvCap);
   const int min_mapq = prm.min_mapq;
-  const int64_t n = DEEP ? dd.n_sel : amb_in ? n_amb_in : n_items;
+  const int64_t n = locus_count<DEEP>(dd, amb_in, n_amb_in, n_items);
   for (int64_t si = gwave; si < n; si += nwaves_total) {
-    const int64_t li = DEEP ? (dd.sel[si] >> 9) : si;
-    const int smp0 = DEEP ? (int)(dd.sel[si] & 255) : 0;
-    bool counted = DEEP ? ((dd.sel[si] >> 8) & 1) != 0 : false;
-    const int64_t it = amb_in ? amb_in[li].item : li;
-    const ComplexItem item = items[it];
-    const Tile tt = tiles[item.tile];
-    const int32_t pos = item.pos;
-    const int32_t win = sw.range_win[tt.range];
-    // a locus (from sample smp on) the working set cannot hold: the deep instantiation's
-    auto hand_over = [&](int smp, uint32_t depth) {
-      if constexpr (!DEEP) {
-        if (lane == 0) {
-          const unsigned long long k = atomicAdd(&ctr->n_deep, 1ull);
-          if (k < dd.cap) dd.out[k] = (li << 9) | (counted ? 256 : 0) | smp;
-          atomicMax(&ctr->deep_max, (unsigned long long)depth);
-        }
-      } else {
-        raise_at(ctr, GQ_E_CAPACITY, pos);
-      }
-    };
-    const Cover ca = make_cover(R, tt.rb, tt.re, pos, m.cov_a, m.ev, m.cap, m.th, sw.wi[2 * win], sw.init_reads,
-                                sw.init_rank, ctr);
-    if (ca.deep) {
-      hand_over(0, (uint32_t)(tt.re - tt.rb));
-      continue;
-    }
+    LocusItem L = locus_item<DEEP>(si, tiles, items, sw, amb_in, dd);
+    Cover ca;
     uint8_t refbase;
-    bool ambiguous;
-    pileup_ref(R, ca, pos, ctr, amb_in ? (int)amb_ref[li] : -1, refbase, ambiguous);
-    if ((item.flags & 1) && !amb_in && !counted) {  // the list kernel did not count this tile's visits
-      uint32_t kept = 0;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        kept += (uint32_t)__popcll(__ballot(act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)));
-      }
-      if (kept && lane == 0) atomicAdd(&ctr->visited, 1ull);
-      counted = true;
-    }
-    if (!amb_in && ambiguous) {  // heap order decides the reference base: list it
-      if (lane == 0) {
-        const unsigned long long k = atomicAdd(&ctr->n_amb, 1ull);
-        if (k < amb_cap) amb_out[k] = AmbItem{item.tile, pos, it};
-      }
+    if (!locus_open<DEEP>(R, L, m, sw, ctr, min_mapq, prm.variants_only, amb_out, amb_cap, amb_in, amb_ref, dd, false, ca,
+                          refbase))
       continue;
-    }
-    if (prm.variants_only && (amb_in || (item.flags & 1))) {  // the list kernel could not decide here
-      bool any = false;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        bool nm = false;
-        if (act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)) {
-          AlleleDesc d;
-          int errc = 0;
-          if (classify(R, r, pos, refbase, d, &errc)) nm = !(d.kind == K_SNV && d.base == refbase);
-        }
-        any |= __ballot(nm) != 0;
-      }
-      if (!any) continue;
-    }
+    const Tile &tt = L.tt;
+    const int32_t pos = L.pos, win = L.win;
+    const int smp0 = L.smp0;
+    auto hand_over = [&](int smp, uint32_t depth) { locus_hand_over<DEEP>(ctr, dd, L, smp, depth); };
     for (int smp = smp0; smp < R.n_samples; ++smp) {
       const Cover cs = R.n_samples == 1 ? ca
                                         : make_cover(R, tt.rb, tt.re, pos, m.cov_s, m.ev, m.cap, m.th, sw.wi[2 * win],

@@ -1,8 +1,9 @@
 // gq_genotype_likelihoods.h — genotype-likelihoods (gq_genotype_likelihoods_call):
 // Likelihood.likelihoodsOfAllPossibleGenotypesFromPileup (likelihood/Likelihood.scala:99-201),
 // logSpace = true, prior 1, for every sample's mapq-filtered pileup at the listed loci.
-// Included by gq_somatic.hip inside its anonymous namespace, after gq_allele_evidence.h (whose
-// allele_evidence_list makes the locus list and whose ae_entry_u32 reads a table column).
+// Included by gq_somatic.hip inside its anonymous namespace, after gq_locus_driver.h (the locus
+// list, the per-locus prologue, the host loop) and gq_allele_evidence.h (whose ae_entry_u32 reads a
+// table column).
 //
 //   genotype_likelihoods_call  one wave per listed locus.  Per sample: the cover list in pileup
 //                              element order and the allele table (make_cover, gather_sample), the
@@ -79,8 +80,6 @@ __device__ __forceinline__ void gl_index(int g, int n, int &i, int &j) {
   j = r + (int)(g - S(r));
 }
 
-// Hand-over entries (dd.out / dd.sel) as allele_evidence_call's: list position << 9 | visit
-// counted << 8 | first sample left.
 template <bool DEEP>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1 : 2))) void genotype_likelihoods_call(
     const Tile *__restrict__ tiles, const ComplexItem *__restrict__ items, int64_t n_items, DevReads R,
@@ -95,79 +94,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   const int64_t gwave = wave_id();
   const int64_t nwaves_total = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  GsMem m;
-  if constexpr (DEEP) {
-    m = gs_deep_mem(dd.scratch + (size_t)gwave * gs_wave_bytes(dd.scap, dd.maxG), dd.scap, dd.maxG);
-  } else {
-    m = GsMem{cover_a[wv], cover_s[wv], work[wv], nullptr, nullptr, nullptr, kCover, kGlTh, kMaxG};
-  }
+  const GsMem m = locus_mem<DEEP>(dd, cover_a[DEEP ? 0 : wv], cover_s[DEEP ? 0 : wv], work[wv], kGlTh, kMaxG);
   GlElem *const eb = reinterpret_cast<GlElem *>(work[wv]);
   double *const ll_lds = reinterpret_cast<double *>(work[wv] + 64 * sizeof(GlElem) / sizeof(uint32_t));
   const int min_mapq = prm.min_mapq;
   const bool incl_align = prm.include_alignment != 0;
-  const int64_t n = DEEP ? dd.n_sel : amb_in ? n_amb_in : n_items;
+  const int64_t n = locus_count<DEEP>(dd, amb_in, n_amb_in, n_items);
   for (int64_t si = gwave; si < n; si += nwaves_total) {
-    const int64_t li = DEEP ? (dd.sel[si] >> 9) : si;
-    const int smp0 = DEEP ? (int)(dd.sel[si] & 255) : 0;
-    bool counted = DEEP ? ((dd.sel[si] >> 8) & 1) != 0 : false;
-    const int64_t it = amb_in ? amb_in[li].item : li;
-    const ComplexItem item = items[it];
-    const Tile tt = tiles[item.tile];
-    const int32_t pos = item.pos;
-    const int32_t win = sw.range_win[tt.range];
-    // a locus (from sample smp on) the working set cannot hold: the deep instantiation's
-    auto hand_over = [&](int smp, uint32_t depth) {
-      if constexpr (!DEEP) {
-        if (lane == 0) {
-          const unsigned long long k = atomicAdd(&ctr->n_deep, 1ull);
-          if (k < dd.cap) dd.out[k] = (li << 9) | (counted ? 256 : 0) | smp;
-          atomicMax(&ctr->deep_max, (unsigned long long)depth);
-        }
-      } else {
-        raise_at(ctr, GQ_E_CAPACITY, pos);
-      }
-    };
-    const Cover ca = make_cover(R, tt.rb, tt.re, pos, m.cov_a, m.ev, m.cap, m.th, sw.wi[2 * win], sw.init_reads,
-                                sw.init_rank, ctr);
-    if (ca.deep) {
-      hand_over(0, (uint32_t)(tt.re - tt.rb));
-      continue;
-    }
+    LocusItem L = locus_item<DEEP>(si, tiles, items, sw, amb_in, dd);
+    Cover ca;
     uint8_t refbase;
-    bool ambiguous;
-    pileup_ref(R, ca, pos, ctr, amb_in ? (int)amb_ref[li] : -1, refbase, ambiguous);
-    if ((item.flags & 1) && !amb_in && !counted) {  // the list kernel did not count this tile's visits
-      uint32_t kept = 0;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        kept += (uint32_t)__popcll(__ballot(act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)));
-      }
-      if (kept && lane == 0) atomicAdd(&ctr->visited, 1ull);
-      counted = true;
-    }
-    if (!amb_in && ambiguous) {  // heap order decides the reference base: list it
-      if (lane == 0) {
-        const unsigned long long k = atomicAdd(&ctr->n_amb, 1ull);
-        if (k < amb_cap) amb_out[k] = AmbItem{item.tile, pos, it};
-      }
+    if (!locus_open<DEEP>(R, L, m, sw, ctr, min_mapq, prm.variants_only, amb_out, amb_cap, amb_in, amb_ref, dd, false, ca,
+                          refbase))
       continue;
-    }
-    if (prm.variants_only && (amb_in || (item.flags & 1))) {  // the list kernel could not decide here
-      bool any = false;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        bool nm = false;
-        if (act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)) {
-          AlleleDesc d;
-          int errc = 0;
-          if (classify(R, r, pos, refbase, d, &errc)) nm = !(d.kind == K_SNV && d.base == refbase);
-        }
-        any |= __ballot(nm) != 0;
-      }
-      if (!any) continue;
-    }
+    const Tile &tt = L.tt;
+    const int32_t pos = L.pos, win = L.win;
+    const int smp0 = L.smp0;
+    auto hand_over = [&](int smp, uint32_t depth) { locus_hand_over<DEEP>(ctr, dd, L, smp, depth); };
     for (int smp = smp0; smp < R.n_samples; ++smp) {
       const Cover cs = R.n_samples == 1 ? ca
                                         : make_cover(R, tt.rb, tt.re, pos, m.cov_s, m.ev, m.cap, m.th, sw.wi[2 * win],

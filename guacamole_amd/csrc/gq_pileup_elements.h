@@ -2,8 +2,9 @@
 // (pileup/Pileup.scala:49-132, pileup/PileupElement.scala) at the listed loci: every element the
 // mapq filter keeps, in Pileup.elements order (gq_winorder.h), with its read, alignment kind,
 // allele, quality score and CIGAR cursor, and the locus' distinct alleles in Allele order.
-// Included by gq_somatic.hip inside its anonymous namespace, after gq_allele_evidence.h (whose
-// allele_evidence_list makes the locus list and whose ae_entry_u32 reads a table column).
+// Included by gq_somatic.hip inside its anonymous namespace, after gq_locus_driver.h (the locus
+// list, the per-locus prologue, the host loop) and gq_allele_evidence.h (whose ae_entry_u32 reads a
+// table column).
 //
 // The output is variable-length per locus (elements, alleles, allele bytes), so it is made in two
 // passes with the sizes scanned in between, all on the device:
@@ -55,7 +56,6 @@ struct PeLayout {  // byte offsets inside the result image
   size_t pool, bytes;
 };
 
-// Hand-over entries (dd.out / dd.sel) as allele_evidence_call's: list position << 9 | visit counted << 8.
 template <bool DEEP>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1 : 2))) void pileup_elements_size(
     const Tile *__restrict__ tiles, const ComplexItem *__restrict__ items, int64_t n_items, DevReads R,
@@ -69,75 +69,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t gwave = wave_id();
   const int64_t nwaves_total = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  GsMem m;
-  if constexpr (DEEP) {
-    m = gs_deep_mem(dd.scratch + (size_t)gwave * gs_wave_bytes(dd.scap, dd.maxG), dd.scap, dd.maxG);
-  } else {
-    m = GsMem{cover_a[wv], nullptr, work[wv], nullptr, nullptr, nullptr, kCover, kPeTh, 0};
-  }
+  const GsMem m = locus_mem<DEEP>(dd, cover_a[DEEP ? 0 : wv], nullptr, work[DEEP ? 0 : wv], kPeTh, 0);
   const int min_mapq = prm.min_mapq;
-  const int64_t n = DEEP ? dd.n_sel : amb_in ? n_amb_in : n_items;
+  const int64_t n = locus_count<DEEP>(dd, amb_in, n_amb_in, n_items);
   for (int64_t si = gwave; si < n; si += nwaves_total) {
-    const int64_t li = DEEP ? (dd.sel[si] >> 9) : si;
-    bool counted = DEEP ? ((dd.sel[si] >> 8) & 1) != 0 : false;
-    const int64_t it = amb_in ? amb_in[li].item : li;
-    const ComplexItem item = items[it];
-    const Tile tt = tiles[item.tile];
-    const int32_t pos = item.pos;
-    const int32_t win = sw.range_win[tt.range];
-    // a locus the working set cannot hold: the deep instantiation's
-    auto hand_over = [&](uint32_t depth) {
-      if constexpr (!DEEP) {
-        if (lane == 0) {
-          const unsigned long long k = atomicAdd(&ctr->n_deep, 1ull);
-          if (k < dd.cap) dd.out[k] = (li << 9) | (counted ? 256 : 0);
-          atomicMax(&ctr->deep_max, (unsigned long long)depth);
-        }
-      } else {
-        raise_at(ctr, GQ_E_CAPACITY, pos);
-      }
-    };
-    const Cover ca = make_cover(R, tt.rb, tt.re, pos, m.cov_a, m.ev, m.cap, m.th, sw.wi[2 * win], sw.init_reads,
-                                sw.init_rank, ctr);
-    if (ca.deep || !ca.compact) {  // (the fill pass stores from the list)
-      hand_over((uint32_t)(tt.re - tt.rb));
-      continue;
-    }
+    LocusItem L = locus_item<DEEP>(si, tiles, items, sw, amb_in, dd);
+    Cover ca;
     uint8_t refbase;
-    bool ambiguous;
-    pileup_ref(R, ca, pos, ctr, amb_in ? (int)amb_ref[li] : -1, refbase, ambiguous);
-    if ((item.flags & 1) && !amb_in && !counted) {  // the list kernel did not count this tile's visits
-      uint32_t kept = 0;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        kept += (uint32_t)__popcll(__ballot(act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)));
-      }
-      if (kept && lane == 0) atomicAdd(&ctr->visited, 1ull);
-      counted = true;
-    }
-    if (!amb_in && ambiguous) {  // heap order decides the reference base: list it
-      if (lane == 0) {
-        const unsigned long long k = atomicAdd(&ctr->n_amb, 1ull);
-        if (k < amb_cap) amb_out[k] = AmbItem{item.tile, pos, it};
-      }
+    // (the fill pass stores from the list: a cover that is not compact is handed over too; no
+    // per-sample pass, so the entry's sample stays 0)
+    if (!locus_open<DEEP>(R, L, m, sw, ctr, min_mapq, prm.variants_only, amb_out, amb_cap, amb_in, amb_ref, dd, true, ca,
+                          refbase))
       continue;
-    }
-    if (prm.variants_only && (amb_in || (item.flags & 1))) {  // the list kernel could not decide here
-      bool any = false;
-      for (int64_t k0 = 0; k0 < ca.n; k0 += 64) {
-        bool act;
-        const int64_t r = ca.read(R, k0 + lane, pos, &act);
-        bool nm = false;
-        if (act && (min_mapq <= 0 || (int)R.mapq[r] >= min_mapq)) {
-          AlleleDesc d;
-          int errc = 0;
-          if (classify(R, r, pos, refbase, d, &errc)) nm = !(d.kind == K_SNV && d.base == refbase);
-        }
-        any |= __ballot(nm) != 0;
-      }
-      if (!any) continue;
-    }
+    const Tile &tt = L.tt;
+    const int32_t pos = L.pos;
+    const int64_t it = L.it;
+    auto hand_over = [&](uint32_t depth) { locus_hand_over<DEEP>(ctr, dd, L, 0, depth); };
     SamplePile<NS> P;
     gather_sample(R, ca, pos, min_mapq, refbase, ctr, P);
     if (P.overflow) {

@@ -304,6 +304,13 @@ __device__ __forceinline__ double wave_sum(double v) {
 // starts from the very bits the reference's arithmetic starts from.
 __constant__ double g_succ[256];
 __device__ __forceinline__ double phred_success(int q) { return g_succ[q > 255 ? 255 : (q < 0 ? 0 : q)]; }
+hipError_t upload_phred_table(gq_ctx *c) {  // phred -> success probability, for the kernels the stream runs next
+  static_assert(sizeof(double) == 8, "FP64");
+  double succ[256];
+  for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
+  const hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
 
 __device__ int success_to_phred(double p) {  // successProbabilityToPhred: round(-10 log10(1 - p)) (Math.round)
   const double x = -10.0 * sm::log10(1.0 - p);
@@ -1253,6 +1260,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
   }
 }
 
+#include "gq_locus_driver.h"
 #include "gq_allele_evidence.h"
 #include "gq_genotype_likelihoods.h"
 #include "gq_pileup_elements.h"
@@ -1291,6 +1299,46 @@ gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_map
   t->dp.put(tab);
   t->mproj_mapq = key;
   return GQ_OK;
+}
+
+// c->keys / c->idx (n pairs) ordered by key into c->keys_sorted / c->idx_sorted: hipcub's radix sort
+// over the bits a key <= key_bound can use.  sort_tmp is sized for the sort and for scan_tmp bytes
+// of the caller's scans that follow.
+gq_status sort_by_key(gq_ctx *c, int64_t n, uint64_t key_bound, size_t scan_tmp = 0) {
+  uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+  uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
+  const int end_bit = std::max(1, 64 - __builtin_clzll(key_bound | 1ull));
+  size_t tmp = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)n, 0, end_bit, c->stream));
+  HIP_TRY(c->sort_tmp.ensure(std::max(tmp, scan_tmp)));
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)n, 0, end_bit,
+                                             c->stream));
+  return GQ_OK;
+}
+
+// gq_timings from a call's events: pileup_ms ev[1]..ev[2], complex_ms ev[2]..ev[3], finalize_ms
+// ev[3]..ev[fin], total_ms ev[0]..ev[4]; where fin is not 4, call_ms ev[fin]..ev[call] (call >= 0)
+// and walk_ms from there to ev[4].  hc: the counters of a command with a deep hand-over.
+void fill_timings(gq_ctx *c, std::chrono::steady_clock::time_point h0, int64_t tiles, const Counters *hc, int fin = 4,
+                  int call = -1) {
+  auto span = [&](int from, int to) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c->ev[from], c->ev[to]);
+    return ms;
+  };
+  c->timings.pileup_ms = span(1, 2);
+  c->timings.complex_ms = span(2, 3);
+  c->timings.finalize_ms = span(3, fin);
+  if (call >= 0) c->timings.call_ms = span(fin, call);
+  if (fin != 4) c->timings.walk_ms = span(call >= 0 ? call : fin, 4);
+  c->timings.total_ms = span(0, 4);
+  c->timings.pileup_launches = 1;
+  c->timings.tiles = tiles;
+  if (hc) {
+    c->timings.deep_loci = (int64_t)hc->n_deep;
+    c->timings.deep_max = (int64_t)hc->deep_max;
+  }
+  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
 }
 
 // The records of a somatic / germline-standard pass (device SomRec array + allele pool) ->
@@ -1584,13 +1632,7 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
     return GQ_OK;
   }
   // PhredUtils.phredToSuccessProbability table: the host's pow, the bits the reference starts from
-  {
-    static_assert(sizeof(double) == 8, "FP64");
-    double succ[256];
-    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
+  HIP_TRY(upload_phred_table(c));
   // pileup element order: each window's first visited locus and initial (heap-ordered) group
   SomWin sw{};
   st = build_somwin(c, pt, t, n, sw);
@@ -1868,24 +1910,11 @@ gq_status gq_somatic_standard_ref(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   }
   res->visited_loci = (int64_t)hc.visited;
   res->candidate_loci = (int64_t)hc.n_complex;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pt.n_tiles;
   c->timings.walk_tiles = (int64_t)hc.n_slow;
-  c->timings.deep_loci = (int64_t)hc.n_deep;
-  c->timings.deep_max = (int64_t)hc.deep_max;
   c->timings.call_ms = call_ms;
   c->timings.deep_ms = deep_ms;
   c->timings.front_ms = 0;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pt.n_tiles, &hc);
   *out = res;
   return GQ_OK;
 }
@@ -2099,12 +2128,7 @@ gq_status gq_germline_standard(gq_ctx *c, const gq_dev_reads *rd, const gq_loci 
     *out = res;
     return GQ_OK;
   }
-  {
-    double succ[256];
-    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
+  HIP_TRY(upload_phred_table(c));
   SomWin sw{};
   st = build_somwin(c, pt, rd, rd, sw);
   if (st) return fail(st);
@@ -2281,138 +2305,37 @@ gq_status gq_allele_evidence(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *l
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  Plan pl;
-  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
-  if (st) return st;
-  st = plan(c, rd, loci, kAeT, pl, c->tiles);
-  if (st) return st;
   gq_allele_evidence_rows *res = (gq_allele_evidence_rows *)calloc(1, sizeof(gq_allele_evidence_rows));
   if (!res) return set_err(GQ_E_NOMEM, "calloc");
   auto fail = [&](gq_status e) {
     gq_free_allele_evidence(res);
     return e;
   };
+  unsigned long long rec_cap = 1 << 16, pool_cap = 1 << 16;
+  ListedLoci ll;
+  const gq_status st = run_listed_loci(
+      c, rd, loci, (int)p->min_mapq, (int)p->variants_only, "allele-evidence", ll,
+      [&](bool deep, unsigned grid, const LocusLaunch &a, const DeepSel &dd) {
+        const auto call = deep ? allele_evidence_call<true> : allele_evidence_call<false>;
+        hipLaunchKernelGGL(call, dim3(grid), dim3(kBlock), 0, c->stream, a.tiles, a.items, a.n_items, rd->d, *p,
+                           (AeRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, a.ctr, a.sw, a.amb_out, a.amb_cap,
+                           a.amb_in, a.amb_ref, a.n_amb_in, dd);
+      },
+      [&](const Counters &hc, int64_t, Growth &grow) -> gq_status {
+        HIP_TRY(c->srecs.ensure(rec_cap * sizeof(AeRec)));
+        HIP_TRY(c->pool.ensure(pool_cap));
+        grow(Growth::OUT0, rec_cap, hc.n_rec, 1024);
+        grow(Growth::OUT0 + 1, pool_cap, hc.pool_used, 4096);
+        return GQ_OK;
+      });
+  if (st) return fail(st);
+  const Plan &pl = ll.pl;
+  const Counters &hc = ll.hc;
+  const int64_t n_items = ll.n_items;
   if (pl.n_tiles == 0) {
     *out = res;
     return GQ_OK;
   }
-  // pileup element order: each window's first visited locus and initial (heap-ordered) group
-  SomWin sw{};
-  st = build_somwin(c, pl, rd, rd, sw);
-  if (st) return fail(st);
-  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
-    c->n_cu = 256;
-  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
-                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
-                     rec_cap = 1 << 16, pool_cap = 1 << 16, amb_cap = 4096, deep_cap = 4096;
-  Counters hc{};
-  int64_t n_items = 0;
-  for (int attempt = 0;; ++attempt) {
-    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
-    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
-    HIP_TRY(c->srecs.ensure(rec_cap * sizeof(AeRec)));
-    HIP_TRY(c->pool.ensure(pool_cap));
-    HIP_TRY(c->counters.ensure(sizeof(Counters)));
-    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
-    Counters *ctr = (Counters *)c->counters.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    // the loci to process, found tile-wise (a few resident workgroups per CU over the tiles)
-    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
-                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)p->min_mapq,
-                       (int)p->variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hc.err) break;
-    if (hc.n_complex > item_cap) {
-      if (attempt == 2) return fail(set_err(GQ_E_CAPACITY, "allele-evidence: locus list capacity retries exhausted"));
-      item_cap = hc.n_complex + 1024;
-      continue;
-    }
-    n_items = (int64_t)hc.n_complex;
-    if (n_items == 0) break;
-    int64_t *dl = (int64_t *)c->deep_list.p;
-    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
-    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
-    // mode, its per-wave scratch sized from the deepest of them
-    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
-                        int64_t n_ain) -> gq_status {
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
-      if (nd <= 0 || hc.err) return GQ_OK;
-      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
-      const int64_t waves = std::min<int64_t>(nd, 256);
-      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
-      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
-      hipLaunchKernelGGL(allele_evidence_call<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)), dim3(kBlock),
-                         0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p,
-                         (AeRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, aout, acap, ain, aref,
-                         n_ain, deep);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      return GQ_OK;
-    };
-    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
-    hipLaunchKernelGGL(allele_evidence_call<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
-                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, (AeRec *)c->srecs.p,
-                       rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, (AmbItem *)c->amb.p, amb_cap,
-                       (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, fast);
-    HIP_TRY(hipGetLastError());
-    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
-    if (st) return fail(st);
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    bool retry = false;
-    if (hc.n_amb > amb_cap) {
-      amb_cap = hc.n_amb + 1024;
-      retry = true;
-    }
-    if (hc.n_deep > deep_cap) {
-      deep_cap = hc.n_deep + 1024;
-      retry = true;
-    }
-    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
-      std::vector<AmbItem> amb((size_t)hc.n_amb);
-      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(c->amb_ref.ensure(amb.size()));
-      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
-      if (st) return fail(st);
-      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
-      const int64_t from = (int64_t)hc.n_deep;
-      hipLaunchKernelGGL(allele_evidence_call<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
-                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p,
-                         (AeRec *)c->srecs.p, rec_cap, (uint8_t *)c->pool.p, pool_cap, ctr, sw, (AmbItem *)nullptr,
-                         (unsigned long long)0, (const AmbItem *)c->amb.p, (const uint8_t *)c->amb_ref.p,
-                         (int64_t)amb.size(), fast);
-      HIP_TRY(hipGetLastError());
-      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
-                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
-      if (st) return fail(st);
-      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-      if (hc.n_deep > deep_cap) {
-        deep_cap = hc.n_deep + 1024;
-        retry = true;
-      }
-    }
-    if (hc.n_rec > rec_cap) {
-      rec_cap = hc.n_rec + 1024;
-      retry = true;
-    }
-    if (hc.pool_used > pool_cap) {
-      pool_cap = hc.pool_used + 4096;
-      retry = true;
-    }
-    if (!retry || hc.err) break;
-    if (attempt == 2) return fail(set_err(GQ_E_CAPACITY, "allele-evidence: output capacity retries exhausted"));
-  }
-  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
-  st = check_device_error(c, hc);
-  if (st) return fail(st);
   const int64_t nr = n_items > 0 ? (int64_t)hc.n_rec : 0;
   std::vector<AeRec> recs((size_t)nr);
   std::vector<uint8_t> hpool((size_t)std::min<unsigned long long>(hc.pool_used, pool_cap));
@@ -2463,20 +2386,7 @@ gq_status gq_allele_evidence(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *l
   res->visited_loci = (int64_t)hc.visited;
   res->listed_loci = n_items;
   c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pl.n_tiles;
-  c->timings.deep_loci = (int64_t)hc.n_deep;
-  c->timings.deep_max = (int64_t)hc.deep_max;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pl.n_tiles, &hc);
   *out = res;
   return GQ_OK;
 }
@@ -2526,137 +2436,39 @@ gq_status genotype_likelihoods_run(gq_ctx *c, const gq_dev_reads *rd, const gq_l
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  Plan pl;
-  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
-  if (st) return st;
-  st = plan(c, rd, loci, kAeT, pl, c->tiles);
-  if (st) return st;
-  if (pl.n_tiles == 0) return GQ_OK;
-  // a buffer that overflowed is grown to what the pass needed and the pass repeated; each buffer
-  // has its own budget of two growths (the heap-order pass can add to what the first one needed)
-  enum { B_ITEM, B_AMB, B_DEEP, B_ALLELE, B_LL, B_POOL, B_N };
-  int grown[B_N] = {};
-  bool spent = false;
-  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
-    if (need <= cap) return false;
-    if (++grown[which] > 2) spent = true;
-    cap = need + slack;
-    return true;
-  };
-  {  // the phred -> success probability table, as the callers fill it
-    double succ[256];
-    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  // pileup element order: each window's first visited locus and initial (heap-ordered) group
-  SomWin sw{};
-  st = build_somwin(c, pl, rd, rd, sw);
-  if (st) return st;
-  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
-    c->n_cu = 256;
-  const gq_allele_evidence_params lp{p->min_mapq, p->variants_only};
-  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
-                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
-                     allele_cap = 0, ll_cap = 0, pool_cap = 1 << 16, amb_cap = 4096, deep_cap = 4096;
-  Counters hc{};
-  int64_t n_items = 0;
-  for (;;) {
-    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
-    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
-    HIP_TRY(c->pool.ensure(pool_cap));
-    HIP_TRY(c->counters.ensure(sizeof(Counters)));
-    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
-    Counters *ctr = (Counters *)c->counters.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    // the loci to process: allele-evidence's list
-    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
-                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)lp.min_mapq,
-                       (int)lp.variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hc.err) break;
-    if (grow(B_ITEM, item_cap, hc.n_complex, 1024)) {
-      if (spent) return set_err(GQ_E_CAPACITY, "genotype-likelihoods: locus list capacity retries exhausted");
-      continue;
-    }
-    n_items = (int64_t)hc.n_complex;
-    if (n_items == 0) break;
-    // a listed locus gives at most one group per sample; alleles and genotypes per group are
-    // guessed (a variant locus mostly holds 2 or 3 alleles) and grown on overflow
-    const unsigned long long group_cap = (unsigned long long)n_items * (unsigned long long)std::max(rd->d.n_samples, 1);
-    allele_cap = std::max(allele_cap, 4 * group_cap + 4096);
-    ll_cap = std::max(ll_cap, 8 * group_cap + 4096);
-    HIP_TRY(c->srecs.ensure(group_cap * sizeof(GlGroup)));
-    HIP_TRY(c->recs.ensure(allele_cap * sizeof(GlAllele)));
-    HIP_TRY(c->recs_sorted.ensure(ll_cap * sizeof(double)));
-    const GlOut go{(GlGroup *)c->srecs.p, group_cap, (GlAllele *)c->recs.p, allele_cap,
+  HIP_TRY(upload_phred_table(c));
+  // a listed locus gives at most one group per sample; alleles and genotypes per group are
+  // guessed (a variant locus mostly holds 2 or 3 alleles) and grown on overflow
+  unsigned long long allele_cap = 0, ll_cap = 0, pool_cap = 1 << 16;
+  GlOut go{};
+  ListedLoci ll;
+  const gq_status st = run_listed_loci(
+      c, rd, loci, (int)p->min_mapq, (int)p->variants_only, "genotype-likelihoods", ll,
+      [&](bool deep, unsigned grid, const LocusLaunch &a, const DeepSel &dd) {
+        const auto call = deep ? genotype_likelihoods_call<true> : genotype_likelihoods_call<false>;
+        hipLaunchKernelGGL(call, dim3(grid), dim3(kBlock), 0, c->stream, a.tiles, a.items, a.n_items, rd->d, *p, go, a.ctr,
+                           a.sw, a.amb_out, a.amb_cap, a.amb_in, a.amb_ref, a.n_amb_in, dd);
+      },
+      [&](const Counters &hc, int64_t n_items, Growth &grow) -> gq_status {
+        const unsigned long long group_cap = (unsigned long long)n_items * (unsigned long long)std::max(rd->d.n_samples, 1);
+        allele_cap = std::max(allele_cap, 4 * group_cap + 4096);
+        ll_cap = std::max(ll_cap, 8 * group_cap + 4096);
+        HIP_TRY(c->pool.ensure(pool_cap));
+        HIP_TRY(c->srecs.ensure(group_cap * sizeof(GlGroup)));
+        HIP_TRY(c->recs.ensure(allele_cap * sizeof(GlAllele)));
+        HIP_TRY(c->recs_sorted.ensure(ll_cap * sizeof(double)));
+        go = GlOut{(GlGroup *)c->srecs.p, group_cap, (GlAllele *)c->recs.p, allele_cap,
                    (double *)c->recs_sorted.p, ll_cap, (uint8_t *)c->pool.p, pool_cap};
-    int64_t *dl = (int64_t *)c->deep_list.p;
-    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
-    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
-    // mode, its per-wave scratch sized from the deepest of them
-    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
-                        int64_t n_ain) -> gq_status {
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
-      if (nd <= 0 || hc.err) return GQ_OK;
-      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
-      const int64_t waves = std::min<int64_t>(nd, 256);
-      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
-      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
-      hipLaunchKernelGGL(genotype_likelihoods_call<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)),
-                         dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items,
-                         rd->d, *p, go, ctr, sw, aout, acap, ain, aref, n_ain, deep);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      return GQ_OK;
-    };
-    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
-    hipLaunchKernelGGL(genotype_likelihoods_call<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
-                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, go, ctr, sw,
-                       (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0, fast);
-    HIP_TRY(hipGetLastError());
-    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
-    if (st) return st;
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    bool retry = grow(B_AMB, amb_cap, hc.n_amb, 1024);
-    retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
-    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
-      std::vector<AmbItem> amb((size_t)hc.n_amb);
-      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(c->amb_ref.ensure(amb.size()));
-      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
-      if (st) return st;
-      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
-      const int64_t from = (int64_t)hc.n_deep;
-      hipLaunchKernelGGL(genotype_likelihoods_call<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
-                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, go, ctr, sw,
-                         (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
-                         (const uint8_t *)c->amb_ref.p, (int64_t)amb.size(), fast);
-      HIP_TRY(hipGetLastError());
-      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
-                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
-      if (st) return st;
-      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-      retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
-    }
-    retry |= grow(B_ALLELE, allele_cap, hc.n_out, 4096);
-    retry |= grow(B_LL, ll_cap, hc.out_pool, 4096);
-    retry |= grow(B_POOL, pool_cap, hc.pool_used, 4096);
-    if (!retry || hc.err) break;
-    if (spent) return set_err(GQ_E_CAPACITY, "genotype-likelihoods: output capacity retries exhausted");
-  }
-  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
-  st = check_device_error(c, hc);
+        grow(Growth::OUT0, allele_cap, hc.n_out, 4096);
+        grow(Growth::OUT0 + 1, ll_cap, hc.out_pool, 4096);
+        grow(Growth::OUT0 + 2, pool_cap, hc.pool_used, 4096);
+        return GQ_OK;
+      });
   if (st) return st;
+  const Plan &pl = ll.pl;
+  const Counters &hc = ll.hc;
+  const int64_t n_items = ll.n_items;
+  if (pl.n_tiles == 0) return GQ_OK;
   // ---- on the device: groups by key, counts scanned to offsets, every column placed; one copy
   const int64_t ng = n_items > 0 ? (int64_t)hc.n_rec : 0;
   const int64_t n_all = ng ? (int64_t)hc.n_out : 0, n_geno = ng ? (int64_t)hc.out_pool : 0;
@@ -2670,20 +2482,16 @@ gq_status genotype_likelihoods_run(gq_ctx *c, const gq_dev_reads *rd, const gq_l
     HIP_TRY(c->idx_sorted.ensure(nn * 4));
     HIP_TRY(c->cands.ensure(6 * nn * sizeof(int64_t)));
     const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
-    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint64_t *keys = (uint64_t *)c->keys.p;
     uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
     int64_t *sc = (int64_t *)c->cands.p;  // (the candidates' buffer: no caller runs beside this one)
     const Gl3 cnt{sc, sc + nn, sc + 2 * nn}, off{sc + 3 * nn, sc + 4 * nn, sc + 5 * nn};
     hipLaunchKernelGGL(gl_keys, dim3(nb), dim3(kBlock), 0, c->stream, (const GlGroup *)c->srecs.p, ng, keys, slot);
     HIP_TRY(hipGetLastError());
-    const uint64_t key_bound = ((uint64_t)pl.n_loci << 12) | 0xFFFu;
-    const int end_bit = 64 - __builtin_clzll(key_bound);
-    size_t tmp = 0, tmp2 = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    size_t tmp2 = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.a, off.a, (int)ng, c->stream));
-    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
-                                               c->stream));
+    const gq_status ss = sort_by_key(c, ng, ((uint64_t)pl.n_loci << 12) | 0xFFFu, tmp2);
+    if (ss) return ss;
     hipLaunchKernelGGL(gl_counts, dim3(nb), dim3(kBlock), 0, c->stream, (const GlGroup *)c->srecs.p,
                        (const uint32_t *)order, ng, cnt);
     HIP_TRY(hipGetLastError());
@@ -2728,22 +2536,7 @@ gq_status genotype_likelihoods_run(gq_ctx *c, const gq_dev_reads *rd, const gq_l
   res->visited_loci = (int64_t)hc.visited;
   res->listed_loci = n_items;
   c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
-  c->timings.walk_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pl.n_tiles;
-  c->timings.deep_loci = (int64_t)hc.n_deep;
-  c->timings.deep_max = (int64_t)hc.deep_max;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pl.n_tiles, &hc, 5);
   return GQ_OK;
 }
 }  // namespace
@@ -2813,123 +2606,29 @@ gq_status pileup_elements_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
   const auto h0 = std::chrono::steady_clock::now();
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  Plan pl;
-  gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
+  unsigned long long rec_cap = 0;
+  ListedLoci ll;
+  gq_status st = run_listed_loci(
+      c, rd, loci, (int)p->min_mapq, (int)p->variants_only, "pileup-elements", ll,
+      [&](bool deep, unsigned grid, const LocusLaunch &a, const DeepSel &dd) {
+        const auto size = deep ? pileup_elements_size<true> : pileup_elements_size<false>;
+        hipLaunchKernelGGL(size, dim3(grid), dim3(kBlock), 0, c->stream, a.tiles, a.items, a.n_items, rd->d, *p,
+                           (PeRec *)c->srecs.p, rec_cap, a.ctr, a.sw, a.amb_out, a.amb_cap, a.amb_in, a.amb_ref, a.n_amb_in,
+                           dd);
+      },
+      [&](const Counters &, int64_t n_items, Growth &) -> gq_status {
+        rec_cap = (unsigned long long)n_items;  // the size pass: one record per listed locus at most
+        HIP_TRY(c->srecs.ensure(rec_cap * sizeof(PeRec)));
+        return GQ_OK;
+      });
   if (st) return st;
-  st = plan(c, rd, loci, kAeT, pl, c->tiles);
-  if (st) return st;
+  const Plan &pl = ll.pl;
+  Counters &hc = ll.hc;
+  Counters *const ctr = ll.ctr;
+  const SomWin &sw = ll.sw;
+  const int64_t n_items = ll.n_items;
   if (pl.n_tiles == 0) return GQ_OK;
-  // a buffer that overflowed is grown to what the pass needed and the pass repeated; each buffer
-  // has its own budget of two growths (the heap-order pass can add to what the first one needed)
-  enum { B_ITEM, B_AMB, B_DEEP, B_N };
-  int grown[B_N] = {};
-  bool spent = false;
-  auto grow = [&](int which, unsigned long long &cap, unsigned long long need, unsigned long long slack) {
-    if (need <= cap) return false;
-    if (++grown[which] > 2) spent = true;
-    cap = need + slack;
-    return true;
-  };
-  // pileup element order: each window's first visited locus and initial (heap-ordered) group
-  SomWin sw{};
-  st = build_somwin(c, pl, rd, rd, sw);
-  if (st) return st;
-  if (c->n_cu <= 0 && hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
-    c->n_cu = 256;
-  unsigned long long item_cap = (unsigned long long)std::min<int64_t>(
-                         pl.n_loci, std::max<int64_t>(pl.n_loci / 8, 1 << 16)),
-                     amb_cap = 4096, deep_cap = 4096;
-  Counters hc{};
-  Counters *ctr = nullptr;
-  int64_t n_items = 0;
-  for (;;) {
-    HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
-    HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
-    HIP_TRY(c->counters.ensure(sizeof(Counters)));
-    HIP_TRY(c->deep_list.ensure(deep_cap * sizeof(int64_t)));
-    ctr = (Counters *)c->counters.p;
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    // the loci to process: allele-evidence's list
-    hipLaunchKernelGGL((allele_evidence_list<kAeT>), dim3((unsigned)std::min<int64_t>(pl.n_tiles, (int64_t)4 * c->n_cu)),
-                       dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, pl.n_tiles, rd->d, (int)p->min_mapq,
-                       (int)p->variants_only, (ComplexItem *)c->cplx.p, item_cap, ctr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hc.err) break;
-    if (grow(B_ITEM, item_cap, hc.n_complex, 1024)) {
-      if (spent) return set_err(GQ_E_CAPACITY, "pileup-elements: locus list capacity retries exhausted");
-      continue;
-    }
-    n_items = (int64_t)hc.n_complex;
-    if (n_items == 0) break;
-    // the size pass: one record per listed locus at most
-    const unsigned long long rec_cap = (unsigned long long)n_items;
-    HIP_TRY(c->srecs.ensure(rec_cap * sizeof(PeRec)));
-    PeRec *recs = (PeRec *)c->srecs.p;
-    int64_t *dl = (int64_t *)c->deep_list.p;
-    const DeepSel fast{dl, deep_cap, nullptr, 0, nullptr, 0, 0};
-    // the loci the fast working set handed over [from, hc.n_deep): the deep instantiation, same
-    // mode, its per-wave scratch sized from the deepest of them
-    auto run_deep = [&](int64_t from, AmbItem *aout, unsigned long long acap, const AmbItem *ain, const uint8_t *aref,
-                        int64_t n_ain) -> gq_status {
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const int64_t nd = (int64_t)std::min<unsigned long long>(hc.n_deep, deep_cap) - from;
-      if (nd <= 0 || hc.err) return GQ_OK;
-      const int scap = (int)std::max<unsigned long long>(hc.deep_max, 64);
-      const int64_t waves = std::min<int64_t>(nd, 256);
-      HIP_TRY(c->deep_scratch.ensure((size_t)waves * gs_wave_bytes(scap, 16) + 256));
-      const DeepSel deep{nullptr, deep_cap, dl + from, nd, (uint8_t *)c->deep_scratch.p, scap, 16};
-      hipLaunchKernelGGL(pileup_elements_size<true>, dim3((unsigned)((waves + kSomWaves - 1) / kSomWaves)),
-                         dim3(kBlock), 0, c->stream, (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items,
-                         rd->d, *p, recs, rec_cap, ctr, sw, aout, acap, ain, aref, n_ain, deep);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&hc, ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      return GQ_OK;
-    };
-    const int cblocks = (int)std::min<int64_t>((n_items + kSomWaves - 1) / kSomWaves, 8192);
-    hipLaunchKernelGGL(pileup_elements_size<false>, dim3((unsigned)cblocks), dim3(kBlock), 0, c->stream,
-                       (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, recs, rec_cap, ctr,
-                       sw, (AmbItem *)c->amb.p, amb_cap, (const AmbItem *)nullptr, (const uint8_t *)nullptr, (int64_t)0,
-                       fast);
-    HIP_TRY(hipGetLastError());
-    st = run_deep(0, (AmbItem *)c->amb.p, amb_cap, nullptr, nullptr, 0);
-    if (st) return st;
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    bool retry = grow(B_AMB, amb_cap, hc.n_amb, 1024);
-    retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
-    if (!retry && hc.n_amb > 0 && !hc.err) {  // heap-order reference bases: replay, then those loci again
-      std::vector<AmbItem> amb((size_t)hc.n_amb);
-      HIP_TRY(hipMemcpyAsync(amb.data(), c->amb.p, amb.size() * sizeof(AmbItem), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(c->amb_ref.ensure(amb.size()));
-      st = heap_ref_bases(c, pl, c->tiles, {rd}, amb, (uint8_t *)c->amb_ref.p);
-      if (st) return st;
-      const int ablocks = (int)std::min<int64_t>(((int64_t)amb.size() + kSomWaves - 1) / kSomWaves, 8192);
-      const int64_t from = (int64_t)hc.n_deep;
-      hipLaunchKernelGGL(pileup_elements_size<false>, dim3((unsigned)ablocks), dim3(kBlock), 0, c->stream,
-                         (const Tile *)c->tiles.p, (const ComplexItem *)c->cplx.p, n_items, rd->d, *p, recs, rec_cap, ctr,
-                         sw, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
-                         (const uint8_t *)c->amb_ref.p, (int64_t)amb.size(), fast);
-      HIP_TRY(hipGetLastError());
-      st = run_deep(from, (AmbItem *)nullptr, (unsigned long long)0, (const AmbItem *)c->amb.p,
-                    (const uint8_t *)c->amb_ref.p, (int64_t)amb.size());
-      if (st) return st;
-      HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-      retry |= grow(B_DEEP, deep_cap, hc.n_deep, 1024);
-    }
-    if (!retry || hc.err) break;
-    if (spent) return set_err(GQ_E_CAPACITY, "pileup-elements: list capacity retries exhausted");
-  }
-  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
   const int64_t visited = (int64_t)hc.visited;
-  st = check_device_error(c, hc);
-  if (st) return st;
   // ---- on the device: the records by call order, their three sizes scanned to offsets, then the
   // fill pass writes every column of the result image; one copy
   const int64_t ng = n_items > 0 ? (int64_t)hc.n_rec : 0;
@@ -2945,21 +2644,17 @@ gq_status pileup_elements_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
     HIP_TRY(c->idx_sorted.ensure(nn * 4));
     HIP_TRY(c->cands.ensure(6 * nn * sizeof(int64_t)));
     const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
-    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint64_t *keys = (uint64_t *)c->keys.p;
     uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
     int64_t *sc = (int64_t *)c->cands.p;  // (the candidates' buffer: no caller runs beside this one)
     const Pe3 cnt{sc, sc + nn, sc + 2 * nn}, off{sc + 3 * nn, sc + 4 * nn, sc + 5 * nn};
     const PeRec *recs = (const PeRec *)c->srecs.p;
     hipLaunchKernelGGL(pe_keys, dim3(nb), dim3(kBlock), 0, c->stream, recs, ng, keys, slot);
     HIP_TRY(hipGetLastError());
-    const uint64_t key_bound = (uint64_t)pl.n_loci;
-    const int end_bit = std::max(1, 64 - __builtin_clzll(key_bound | 1ull));
-    size_t tmp = 0, tmp2 = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    size_t tmp2 = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.a, off.a, (int)ng, c->stream));
-    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
-                                               c->stream));
+    st = sort_by_key(c, ng, (uint64_t)pl.n_loci, tmp2);
+    if (st) return st;
     hipLaunchKernelGGL(pe_counts, dim3(nb), dim3(kBlock), 0, c->stream, recs, (const uint32_t *)order, ng, cnt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->sort_tmp.p, tmp2, cnt.e, off.e, (int)ng, c->stream));
@@ -3029,24 +2724,7 @@ gq_status pileup_elements_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *
   res->listed_loci = n_items;
   res->block_bytes = (int64_t)lay.bytes;
   c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
-  c->timings.call_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[6], c->ev[4]);
-  c->timings.walk_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pl.n_tiles;
-  c->timings.deep_loci = (int64_t)hc.n_deep;
-  c->timings.deep_max = (int64_t)hc.deep_max;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pl.n_tiles, &hc, 5, 6);
   return GQ_OK;
 }
 }  // namespace
@@ -3254,20 +2932,7 @@ gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *lo
   res->visited_loci = (int64_t)hc.visited;
   res->listed_loci = n_items;
   res->block_bytes = (int64_t)lay.bytes;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
-  c->timings.walk_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pl.n_tiles;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pl.n_tiles, nullptr, 5);
   return GQ_OK;
 }
 }  // namespace
@@ -3360,12 +3025,7 @@ gq_status somatic_likelihoods_run(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   st = plan(c, n, loci, SomProjCfg::kT, pn, c->tiles2, 0, 0, 0, true);
   if (st) return st;
   if (pt.n_tiles == 0) return GQ_OK;
-  {  // the phred -> success probability table, as the callers fill it
-    double succ[256];
-    for (int q = 0; q < 256; ++q) succ[q] = 1.0 - std::pow(10.0, -q / 10.0);
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_succ), succ, sizeof succ, 0, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
+  HIP_TRY(upload_phred_table(c));
   SomWin sw{};
   st = build_somwin(c, pt, t, n, sw);
   if (st) return st;
@@ -3593,21 +3253,17 @@ gq_status somatic_likelihoods_run(gq_ctx *c, const gq_dev_reads *t, const gq_dev
     HIP_TRY(c->idx_sorted.ensure(nn * 4));
     HIP_TRY(c->cands.ensure(10 * nn * sizeof(int64_t)));
     const unsigned nb = (unsigned)((ng + kBlock - 1) / kBlock);
-    uint64_t *keys = (uint64_t *)c->keys.p, *keys2 = (uint64_t *)c->keys_sorted.p;
+    uint64_t *keys = (uint64_t *)c->keys.p;
     uint32_t *slot = (uint32_t *)c->idx.p, *order = (uint32_t *)c->idx_sorted.p;
     int64_t *sc = (int64_t *)c->cands.p;  // (the listed loci's records: every per-locus kernel is done)
     const Sl5 cnt{sc, sc + nn, sc + 2 * nn, sc + 3 * nn, sc + 4 * nn},
         off{sc + 5 * nn, sc + 6 * nn, sc + 7 * nn, sc + 8 * nn, sc + 9 * nn};
     hipLaunchKernelGGL(sl_keys, dim3(nb), dim3(kBlock), 0, c->stream, (const SlGroup *)c->srecs.p, ng, keys, slot);
     HIP_TRY(hipGetLastError());
-    const uint64_t key_bound = (uint64_t)std::max<int64_t>(pt.n_loci, 1);
-    const int end_bit = 64 - __builtin_clzll(key_bound);
-    size_t tmp = 0, tmp2 = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit, c->stream));
+    size_t tmp2 = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, cnt.ta, off.ta, (int)ng, c->stream));
-    HIP_TRY(c->sort_tmp.ensure(std::max(tmp, tmp2)));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, keys, keys2, slot, order, (int)ng, 0, end_bit,
-                                               c->stream));
+    st = sort_by_key(c, ng, (uint64_t)pt.n_loci, tmp2);
+    if (st) return st;
     hipLaunchKernelGGL(sl_counts, dim3(nb), dim3(kBlock), 0, c->stream, (const SlGroup *)c->srecs.p,
                        (const uint32_t *)order, ng, cnt);
     HIP_TRY(hipGetLastError());
@@ -3693,24 +3349,9 @@ gq_status somatic_likelihoods_run(gq_ctx *c, const gq_dev_reads *t, const gq_dev
   res->listed_loci = (int64_t)n_cand;
   res->block_bytes = (int64_t)lay.bytes;
   c->timings.marshal_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m0).count();
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timings.pileup_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-  c->timings.complex_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[5]);
-  c->timings.finalize_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[4]);
-  c->timings.walk_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]);
-  c->timings.total_ms = ms;
-  c->timings.pileup_launches = 1;
-  c->timings.tiles = pt.n_tiles;
   c->timings.walk_tiles = (int64_t)hc.n_slow;
-  c->timings.deep_loci = (int64_t)hc.n_deep;
-  c->timings.deep_max = (int64_t)hc.deep_max;
   c->timings.deep_ms = deep_ms;
-  c->timings.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  fill_timings(c, h0, pt.n_tiles, &hc, 5);
   return GQ_OK;
 }
 }  // namespace

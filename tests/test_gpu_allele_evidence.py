@@ -316,6 +316,72 @@ def test_empty_inputs_give_no_rows(gpu_ctx):
     assert len(res) == 0 and res.visited_loci == 0
 
 
+# ---- 6b. a second round of the listed-locus loop ----------------------------------------------
+GROWTH_LEN, GROWTH_MID = 70_000, 35_000
+
+
+@functools.lru_cache(maxsize=None)
+def growth_reads():
+    """About 70,000 loci at depth ~4 whose coverage breaks at GROWTH_MID: no read spans it, and one
+    read only starts at the first covered locus past it, so a call that starts at GROWTH_MID begins
+    with a one-read pileup group whose heap order is its input order, as in the whole call."""
+    rs = generate(GROWTH_LEN, 4, seed=29).to_read_set()
+    s, e = np.asarray(rs.start), np.asarray(rs.end)
+    keep = (e <= GROWTH_MID) | (s >= GROWTH_MID)
+    first = s[keep & (s >= GROWTH_MID)].min()
+    keep[np.nonzero(keep & (s == first))[0][1:]] = False
+    return rs.subset(np.nonzero(keep)[0])
+
+
+def position_free(res, firsts):
+    """A result's columns with nothing that depends on where the result starts: the allele offsets
+    replaced by the bytes they point at, each `*_first` column of firsts = {name: counts(cols)}
+    checked to be the exclusive sum of its counts and dropped."""
+    c = dict(res.cols)
+    out = {}
+    for side in ("ref", "alt"):
+        out[side] = [res.pool[o:o + n] for o, n in zip(c.pop(side + "_off").tolist(), c[side + "_len"].tolist())]
+    for name, counts in firsts.items():
+        n = np.asarray(counts(c), np.int64)
+        assert np.array_equal(c.pop(name), np.cumsum(n) - n), name
+    out.update(c)
+    return out
+
+
+def check_list_growth_round(call, firsts):
+    """call(loci) over the whole of growth_reads (variants_only = 0: every covered locus is listed,
+    more than the list's first capacity of 65,536, so the loop runs a second round) equals, field
+    for field and bit for bit, the calls over its two halves (each under 65,536 loci) put together.
+    Preconditions: no read spans the split (checked here on the reads); no row or group of any of
+    the three results has its reference base from heap order (flag bit0)."""
+    rs = growth_reads()
+    s, e = np.asarray(rs.start), np.asarray(rs.end)
+    assert not np.any((s < GROWTH_MID) & (e > GROWTH_MID))
+    assert np.count_nonzero(s == s[s >= GROWTH_MID].min()) == 1
+    whole = call(rs, loci_of(rs, "20:0-%d" % GROWTH_LEN))
+    halves = [call(rs, loci_of(rs, "20:0-%d" % GROWTH_MID)), call(rs, loci_of(rs, "20:%d-%d" % (GROWTH_MID, GROWTH_LEN)))]
+    assert whole.listed_loci > 65536 and all(0 < h.listed_loci < 65536 for h in halves)
+    assert whole.listed_loci == sum(h.listed_loci for h in halves)
+    assert whole.visited_loci == sum(h.visited_loci for h in halves)
+    w, (a, b) = position_free(whole, firsts), [position_free(h, firsts) for h in halves]
+    assert not any((x["flags"] & 1).any() for x in (w, a, b))
+    assert len(whole) == len(halves[0]) + len(halves[1])
+    for k, v in w.items():
+        if isinstance(v, list):
+            assert a[k] + b[k] == v, k
+        else:
+            both = np.concatenate([a[k], b[k]])
+            assert both.dtype == v.dtype and both.tobytes() == v.tobytes(), k
+    return whole
+
+
+def test_list_growth_round(gpu_ctx):
+    """More listed loci than the list first holds, and more rows than the row buffer (both 65,536)."""
+    whole = check_list_growth_round(
+        lambda rs, loci: gpu_ctx.allele_evidence(device_reads(gpu_ctx, rs), loci, min_mapq=1, variants_only=False), {})
+    assert len(whole) > 65536
+
+
 # ---- 7. tasks --------------------------------------------------------------------------------
 def test_rows_do_not_depend_on_the_task_count(gpu_ctx):
     rs = chrm()

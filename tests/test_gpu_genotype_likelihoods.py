@@ -24,7 +24,7 @@ from oracle import oracle as O
 
 from test_allele_evidence import first_pileup_zone, in_zone, kept, loci_of
 from test_genotype_likelihoods import covering, strict_exp
-from test_gpu_allele_evidence import chrm, dropped_cover, synthetic, two_samples
+from test_gpu_allele_evidence import check_list_growth_round, chrm, dropped_cover, synthetic, two_samples
 
 pytestmark = pytest.mark.gpu
 
@@ -335,6 +335,14 @@ def test_empty_inputs_give_no_groups(gpu_ctx):
     res = gpu_ctx.genotype_likelihoods(device_reads(gpu_ctx, far), loci_of(far, "chr1:0-500"), min_mapq=0,
                                        variants_only=False)
     assert len(res) == 0 and res.n_genotypes == 0 and res.visited_loci == 0
+
+
+def test_list_growth_round(gpu_ctx):
+    """More listed loci than the list first holds (65,536): see check_list_growth_round."""
+    check_list_growth_round(
+        lambda rs, loci: gpu_ctx.genotype_likelihoods(device_reads(gpu_ctx, rs), loci, min_mapq=1, variants_only=False),
+        {"allele_first": lambda c: c["n_alleles"],
+         "geno_first": lambda c: c["n_alleles"].astype(np.int64) * (c["n_alleles"] + 1) // 2})
 
 
 # ---- 6. CLI -----------------------------------------------------------------------------------

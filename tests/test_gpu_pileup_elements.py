@@ -19,7 +19,7 @@ from guacamole_amd.reads import load_reads, make_read as mr, make_read_set
 from oracle import oracle as O
 
 from test_allele_evidence import FILTERS, first_pileup_zone, in_zone, kept, loci_of
-from test_gpu_allele_evidence import chrm, dropped_cover, synthetic, two_samples
+from test_gpu_allele_evidence import check_list_growth_round, chrm, dropped_cover, synthetic, two_samples
 from test_pileup_elements import ELEMENT_FIELDS, ExpectedPileups, alleles_of
 
 pytestmark = pytest.mark.gpu
@@ -225,6 +225,13 @@ def test_a_small_call_after_a_large_one(gpu_ctx):
         assert pileup_elements_reads(fresh, rs, big, variants_only=False) == a_big
     finally:
         fresh.close()
+
+
+def test_list_growth_round(gpu_ctx):
+    """More listed loci than the list first holds (65,536): see check_list_growth_round."""
+    check_list_growth_round(
+        lambda rs, loci: gpu_ctx.pileup_elements(device_reads(gpu_ctx, rs), loci, min_mapq=1, variants_only=False),
+        {"elem_first": lambda c: c["depth"], "allele_first": lambda c: c["n_alleles"]})
 
 
 # ---- 9. empty and error inputs ----------------------------------------------------------------
