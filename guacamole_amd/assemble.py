@@ -100,6 +100,17 @@ def window_references(reference_contigs: Dict[str, Optional[np.ndarray]], window
     return out
 
 
+def graphs_and_paths(ctx, device_reads, device_reference, windows, contig_names: Sequence[str], k: int = 25,
+                     min_occurrence: int = 1, max_paths: int = 10, max_path_length: Optional[int] = None,
+                     max_steps: Optional[int] = None, min_mapq: int = 0):
+    """The windows' graphs (device) and their haplotypes and unitigs (host): (AsmGraphs, paths)."""
+    index = {n: i for i, n in enumerate(contig_names)}
+    graphs = ctx.asm_graphs(device_reads, device_reference, [index[c] for c, _, _ in windows],
+                            [s for _, s, _ in windows], [e for _, _, e in windows], k=k, min_occurrence=min_occurrence,
+                            min_mapq=min_mapq)
+    return graphs, graphs.paths(max_paths=max_paths, max_path_length=max_path_length, max_steps=max_steps)
+
+
 def assemble_windows(ctx, device_reads, device_reference, windows, contig_names: Sequence[str],
                      reference_contigs: Dict[str, Optional[np.ndarray]], k: int = 25, min_occurrence: int = 1,
                      max_paths: int = 10, max_path_length: Optional[int] = None, max_steps: Optional[int] = None,
@@ -107,11 +118,8 @@ def assemble_windows(ctx, device_reads, device_reference, windows, contig_names:
     """Assemble every window (contig name, start, end) of the resident reads: rows as in TSV_HEADER
     (plus `aligned`).  contig_names: the read set's contig list; reference_contigs: the bytes the
     resident reference was uploaded from, by name.  info (a dict) receives the spans."""
-    index = {n: i for i, n in enumerate(contig_names)}
-    graphs = ctx.asm_graphs(device_reads, device_reference, [index[c] for c, _, _ in windows],
-                            [s for _, s, _ in windows], [e for _, _, e in windows], k=k, min_occurrence=min_occurrence,
-                            min_mapq=min_mapq)
-    paths = graphs.paths(max_paths=max_paths, max_path_length=max_path_length, max_steps=max_steps)
+    graphs, paths = graphs_and_paths(ctx, device_reads, device_reference, windows, contig_names, k, min_occurrence,
+                                     max_paths, max_path_length, max_steps, min_mapq)
     refs = window_references(reference_contigs, windows)
     alignments, unaligned = align_haplotypes(paths, refs, ctx.align_batch, **probabilities)
     if info is not None:

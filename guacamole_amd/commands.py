@@ -1431,12 +1431,86 @@ def assemble_windows_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def haplotype_likelihoods_main(argv: Sequence[str]) -> int:
+    """haplotype-likelihoods: assemble-windows up to the haplotypes, then every window read against
+    every haplotype (a pair-HMM forward pass) and the diploid genotype likelihoods over the window's
+    haplotypes (Likelihood.likelihoodsOfGenotypes over reads), one TSV line per genotype."""
+    import os
+    from . import assemble, haplotypes
+    from .reference import ReferenceGenome
+    p = argparse.ArgumentParser(prog="haplotype-likelihoods",
+                                description="likelihoods of the reads under the assembled haplotypes of each window")
+    p.add_argument("--reads", required=True, help="Aligned reads")
+    p.add_argument("--reference-fasta", required=True, help="Local path to a reference FASTA file")
+    p.add_argument("--loci", default="all", help="Loci to cut into windows (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--out", required=True, help="Output TSV path of the genotype rows (must not exist)")
+    p.add_argument("--out-reads", default="", help="Also write one row per window read: its log-likelihood per haplotype")
+    p.add_argument("--kmer-size", type=int, default=25)
+    p.add_argument("--min-occurrence", type=int, default=2, help="Occurrences a k-mer needs to be a node")
+    p.add_argument("--window-size", type=int, default=200)
+    p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
+    p.add_argument("--max-paths", type=int, default=10)
+    p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--quality-floor", type=int, default=None, help="Base qualities below it count as it (6)")
+    p.add_argument("--mismatch-probability", type=float, default=None, help="For reads without qualities")
+    p.add_argument("--open-gap-probability", type=float, default=None)
+    p.add_argument("--close-gap-probability", type=float, default=None)
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("haplotype-likelihoods")
+    for path in (args.out, args.out_reads):
+        if path and os.path.lexists(path):
+            raise FileExistsError("Output path %s already exists" % path)
+    clock = StageClock()
+    # the reads as stored, as assemble-windows loads them
+    load_args = argparse.Namespace(reference_fasta="", recompute_md_tags=False, device=args.device)
+    ctx, (rs,) = load_product_reads(load_args, InputFilters.make(mapped=True, non_duplicate=True), args.reads)
+    if ctx is None:
+        ctx = native.Context(args.device)
+    dr = device_reads(ctx, rs)
+    clock.mark("load_reads")
+    names = list(rs.contig_names)
+    contigs = ReferenceGenome.load_fasta(args.reference_fasta).for_contigs(names)
+    dref = ctx.upload_reference(contigs)
+    clock.mark("load_reference")
+    loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
+    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                   args.window_step or None, args.kmer_size)
+    info: dict = {}
+    try:
+        graphs, paths = assemble.graphs_and_paths(ctx, dr, dref, windows, names, k=args.kmer_size,
+                                                  min_occurrence=args.min_occurrence, max_paths=args.max_paths,
+                                                  min_mapq=args.min_mapq)
+        clock.mark("assemble")
+        rows, reads = haplotypes.haplotype_likelihoods(
+            ctx, dr, dref, graphs, paths, windows, names, min_mapq=args.min_mapq, with_reads=bool(args.out_reads),
+            info=info, quality_floor=args.quality_floor, mismatch_probability=args.mismatch_probability,
+            open_gap_probability=args.open_gap_probability, close_gap_probability=args.close_gap_probability)
+    finally:
+        dref.free()
+    clock.mark("likelihoods")
+    with open(args.out, "w") as fh:
+        fh.write(haplotypes.GENOTYPE_HEADER + "\n")
+        fh.writelines(l + "\n" for l in haplotypes.genotype_tsv_lines(rows))
+    if args.out_reads:
+        with open(args.out_reads, "w") as fh:
+            fh.write(haplotypes.READ_HEADER + "\n")
+            fh.writelines(l + "\n" for l in haplotypes.read_tsv_lines(reads))
+    clock.mark("write")
+    print("%d windows, %d read-haplotype pairs (%d underflowed), %d genotypes; wrote %d rows." %
+          (len(windows), info["n_pairs"], info["n_underflow"], info["n_genotypes"], len(rows)), file=sys.stderr)
+    clock.report(windows=len(windows), graphs_ms=graphs.info["ms"], paths_ms=paths["ms"], haplik_ms=info["haplik_ms"],
+                 kernel_ms=info["haplik_kernel_ms"], genotype_ms=info["genotype_ms"])
+    return 0
+
+
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
             "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main,
-            "realign-reads": realign_reads_main, "assemble-windows": assemble_windows_main}
+            "realign-reads": realign_reads_main, "assemble-windows": assemble_windows_main,
+            "haplotype-likelihoods": haplotype_likelihoods_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

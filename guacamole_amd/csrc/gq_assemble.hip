@@ -11,6 +11,7 @@
 #include "gq_host.h"
 #include "gq_assemble_host.h"
 #include "gq_assemble.h"
+#include "gq_winreads.h"
 
 using namespace gq;
 
@@ -271,6 +272,62 @@ gq_status launch_chunked(Run &r, bool lds, const std::vector<int64_t> &ids, int6
 
 }  // namespace
 
+namespace gq {
+
+gq_status find_window_reads(gq_ctx *c, const gq_dev_reads *d, int64_t W, const int32_t *contig, const int32_t *start,
+                            const int32_t *end, int32_t k, int32_t min_mapq, const char *who, WindowReads &out) {
+  out.W = W;
+  const size_t w1 = (size_t)W + 1;
+  DevBuf *d_win = &out.win, *d_cnt = &out.cnt, *d_coff = &out.coff, *d_ra = &out.ra, *d_tmp = &out.tmp;
+  HIP_TRY(d_win->ensure(4 * 3 * (size_t)W));
+  HIP_TRY(d_cnt->ensure(8 * w1));
+  HIP_TRY(d_coff->ensure(8 * w1));
+  HIP_TRY(d_ra->ensure(8 * (size_t)W));
+  int32_t *dw = (int32_t *)d_win->p;
+  HIP_TRY(hipMemcpyAsync(dw, contig, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dw + W, start, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dw + 2 * W, end, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
+  const asmk::Windows win{dw, dw + W, dw + 2 * W};
+  hipLaunchKernelGGL(asmk::asm_range_k, dim3((unsigned)((W + 1 + 255) / 256)), dim3(256), 0, c->stream, d->d, W, win,
+                     (int64_t *)d_cnt->p, (int64_t *)d_ra->p);
+  HIP_TRY(hipGetLastError());
+  size_t tb = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t *)d_cnt->p, (int64_t *)d_coff->p, (int)w1,
+                                           c->stream));
+  HIP_TRY(d_tmp->ensure(tb));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp->p, tb, (const int64_t *)d_cnt->p, (int64_t *)d_coff->p, (int)w1,
+                                           c->stream));
+  int64_t C = 0;
+  HIP_TRY(hipMemcpyAsync(&C, (const int64_t *)d_coff->p + W, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (C + 1 >= ((int64_t)1 << 31))
+    return set_err(GQ_E_CAPACITY, "%s: %lld candidate reads over the windows of one call", who, (long long)C);
+  out.C = C;
+  const size_t c1 = (size_t)C + 1;
+  DevBuf *d_flag = &out.flag, *d_inst = &out.inst, *d_chunks = &out.chunks, *d_fsum = &out.fsum, *d_isum = &out.isum,
+         *d_csum = &out.csum, *d_lr = &out.list_read, *d_lc = &out.list_chunk;
+  for (DevBuf *b : {d_flag, d_inst, d_chunks, d_fsum, d_isum, d_csum, d_lr, d_lc}) HIP_TRY(b->ensure(8 * c1));
+  hipLaunchKernelGGL(asmk::asm_test_k, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, c->stream, d->d, W, win, k,
+                     min_mapq, (const int64_t *)d_coff->p, (const int64_t *)d_ra->p, C, (int64_t *)d_flag->p, (int64_t *)d_inst->p,
+                     (int64_t *)d_chunks->p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t *)d_flag->p, (int64_t *)d_fsum->p, (int)c1,
+                                           c->stream));
+  HIP_TRY(d_tmp->ensure(tb));
+  for (auto io : {std::make_pair(d_flag, d_fsum), std::make_pair(d_inst, d_isum), std::make_pair(d_chunks, d_csum)})
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp->p, tb, (const int64_t *)io.first->p, (int64_t *)io.second->p,
+                                             (int)c1, c->stream));
+  if (C > 0) {
+    hipLaunchKernelGGL(asmk::asm_compact_k, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, c->stream, W,
+                       (const int64_t *)d_coff->p, (const int64_t *)d_ra->p, C, (const int64_t *)d_flag->p,
+                       (const int64_t *)d_fsum->p, (const int64_t *)d_csum->p, (int64_t *)d_lr->p, (int64_t *)d_lc->p);
+    HIP_TRY(hipGetLastError());
+  }
+  return GQ_OK;
+}
+
+}  // namespace gq
+
 extern "C" {
 
 void gq_asm_default_params(gq_asm_params *out) {
@@ -357,54 +414,14 @@ gq_status gq_asm_graphs(gq_ctx *c, const gq_dev_reads *d, const gq_reference *re
   HIP_TRY(rs.make());
   HIP_TRY(hipEventRecord(span.a, c->stream));
   HIP_TRY(hipEventRecord(rs.a, c->stream));
-  const size_t w1 = (size_t)W + 1;
+  WindowReads wr;
+  if ((s = find_window_reads(c, d, W, contig, start, end, p.k, p.min_mapq, "gq_asm_graphs", wr))) return s;
   Bufs bufs;
-  DevBuf *d_win = bufs.add(), *d_cnt = bufs.add(), *d_coff = bufs.add(), *d_ra = bufs.add(), *d_tmp = bufs.add(),
-         *d_meta = bufs.add();
-  HIP_TRY(d_win->ensure(4 * 3 * (size_t)W));
-  HIP_TRY(d_cnt->ensure(8 * w1));
-  HIP_TRY(d_coff->ensure(8 * w1));
-  HIP_TRY(d_ra->ensure(8 * (size_t)W));
+  DevBuf *d_meta = bufs.add();
   HIP_TRY(d_meta->ensure(sizeof(asmk::WinMeta) * (size_t)W));
-  int32_t *dw = (int32_t *)d_win->p;
-  HIP_TRY(hipMemcpyAsync(dw, contig, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dw + W, start, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dw + 2 * W, end, 4 * (size_t)W, hipMemcpyHostToDevice, c->stream));
-  const asmk::Windows win{dw, dw + W, dw + 2 * W};
-  hipLaunchKernelGGL(asmk::asm_range_k, dim3((unsigned)((W + 1 + 255) / 256)), dim3(256), 0, c->stream, d->d, W, win,
-                     (int64_t *)d_cnt->p, (int64_t *)d_ra->p);
-  HIP_TRY(hipGetLastError());
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t *)d_cnt->p, (int64_t *)d_coff->p, (int)w1,
-                                           c->stream));
-  HIP_TRY(d_tmp->ensure(tb));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp->p, tb, (const int64_t *)d_cnt->p, (int64_t *)d_coff->p, (int)w1,
-                                           c->stream));
-  int64_t C = 0;
-  HIP_TRY(hipMemcpyAsync(&C, (const int64_t *)d_coff->p + W, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (C + 1 >= ((int64_t)1 << 31))
-    return set_err(GQ_E_CAPACITY, "gq_asm_graphs: %lld candidate reads over the windows of one call", (long long)C);
-  const size_t c1 = (size_t)C + 1;
-  DevBuf *d_flag = bufs.add(), *d_inst = bufs.add(), *d_chunks = bufs.add(), *d_fsum = bufs.add(), *d_isum = bufs.add(),
-         *d_csum = bufs.add(), *d_lr = bufs.add(), *d_lc = bufs.add();
-  for (DevBuf *b : {d_flag, d_inst, d_chunks, d_fsum, d_isum, d_csum, d_lr, d_lc}) HIP_TRY(b->ensure(8 * c1));
-  hipLaunchKernelGGL(asmk::asm_test_k, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, c->stream, d->d, W, win, p.k,
-                     p.min_mapq, (const int64_t *)d_coff->p, (const int64_t *)d_ra->p, C, (int64_t *)d_flag->p, (int64_t *)d_inst->p,
-                     (int64_t *)d_chunks->p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t *)d_flag->p, (int64_t *)d_fsum->p, (int)c1,
-                                           c->stream));
-  HIP_TRY(d_tmp->ensure(tb));
-  for (auto io : {std::make_pair(d_flag, d_fsum), std::make_pair(d_inst, d_isum), std::make_pair(d_chunks, d_csum)})
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp->p, tb, (const int64_t *)io.first->p, (int64_t *)io.second->p,
-                                             (int)c1, c->stream));
-  if (C > 0) {
-    hipLaunchKernelGGL(asmk::asm_compact_k, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, c->stream, W,
-                       (const int64_t *)d_coff->p, (const int64_t *)d_ra->p, C, (const int64_t *)d_flag->p,
-                       (const int64_t *)d_fsum->p, (const int64_t *)d_csum->p, (int64_t *)d_lr->p, (int64_t *)d_lc->p);
-    HIP_TRY(hipGetLastError());
-  }
+  const asmk::Windows win{wr.contig(), wr.start(), wr.end()};
+  DevBuf *d_coff = &wr.coff, *d_fsum = &wr.fsum, *d_isum = &wr.isum, *d_csum = &wr.csum, *d_lr = &wr.list_read,
+         *d_lc = &wr.list_chunk;
   hipLaunchKernelGGL(asmk::asm_meta_k, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, c->stream, W,
                      (const int64_t *)d_coff->p, (const int64_t *)d_fsum->p, (const int64_t *)d_isum->p,
                      (const int64_t *)d_csum->p, (asmk::WinMeta *)d_meta->p);

@@ -304,6 +304,26 @@ class gq_asm_path_block(C.Structure):
                 ("reserved", C.c_int32), ("block_", C.c_void_p)]
 
 
+class gq_haplik_params(C.Structure):
+    _fields_ = [("mismatch_probability", C.c_double), ("open_gap_probability", C.c_double),
+                ("close_gap_probability", C.c_double), ("quality_floor", C.c_double), ("reserved", C.c_double * 4)]
+
+
+class gq_haplik_pairs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("scaled", C.POINTER(C.c_double)), ("log_likelihood", C.POINTER(C.c_double)),
+                ("flags", C.POINTER(C.c_uint8)), ("ms", C.c_float), ("kernel_ms", C.c_float), ("block_", C.c_void_p)]
+
+
+class gq_haplik_block(C.Structure):
+    _fields_ = [("n_windows", C.c_int64), ("n_reads", C.c_int64), ("n_pairs", C.c_int64), ("n_genotypes", C.c_int64),
+                ("win_read_off", C.POINTER(C.c_int64)), ("win_reads", C.POINTER(C.c_int64)),
+                ("lik_off", C.POINTER(C.c_int64)), ("scaled", C.POINTER(C.c_double)),
+                ("log_likelihood", C.POINTER(C.c_double)), ("flags", C.POINTER(C.c_uint8)),
+                ("gt_off", C.POINTER(C.c_int64)), ("gt_log_likelihood", C.POINTER(C.c_double)),
+                ("best_genotype", C.POINTER(C.c_int32)), ("ms", C.c_float), ("reads_ms", C.c_float),
+                ("kernel_ms", C.c_float), ("genotype_ms", C.c_float), ("block_", C.c_void_p)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -326,7 +346,9 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_align_default_params", "gq_align_penalties", "gq_align_limits", "gq_align_batch", "gq_align_host",
             "gq_free_alignments", "gq_align_reads", "gq_align_free_index",
             "gq_asm_default_params", "gq_asm_limits", "gq_asm_graphs", "gq_asm_graphs_host", "gq_asm_free_graphs",
-            "gq_asm_paths", "gq_asm_free_paths")
+            "gq_asm_paths", "gq_asm_free_paths",
+            "gq_haplik_default_params", "gq_haplik_tables", "gq_haplik_batch", "gq_haplik_host", "gq_haplik_free_pairs",
+            "gq_haplik_windows", "gq_haplik_free_block", "gq_haplik_genotypes_host")
 
 
 def lib():
@@ -488,6 +510,24 @@ def lib():
                                    C.POINTER(C.POINTER(gq_asm_path_block))]
         L.gq_asm_free_paths.argtypes = [C.POINTER(gq_asm_path_block)]
         L.gq_asm_free_paths.restype = None
+        for f in ("gq_haplik_tables", "gq_haplik_batch", "gq_haplik_host", "gq_haplik_windows",
+                  "gq_haplik_genotypes_host"):
+            getattr(L, f).restype = C.c_int
+        L.gq_haplik_default_params.argtypes = [C.POINTER(gq_haplik_params)]
+        L.gq_haplik_default_params.restype = None
+        L.gq_haplik_tables.argtypes = [C.POINTER(gq_haplik_params)] + [C.POINTER(C.c_double)] * 3
+        L.gq_haplik_batch.argtypes = [vp, C.c_int64] + [vp] * 7 + [C.POINTER(gq_haplik_params),
+                                                                   C.POINTER(C.POINTER(gq_haplik_pairs))]
+        L.gq_haplik_host.argtypes = [C.c_int64] + [vp] * 7 + [C.POINTER(gq_haplik_params), C.c_int32,
+                                                              C.POINTER(C.POINTER(gq_haplik_pairs))]
+        L.gq_haplik_free_pairs.argtypes = [C.POINTER(gq_haplik_pairs)]
+        L.gq_haplik_free_pairs.restype = None
+        L.gq_haplik_windows.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.POINTER(gq_asm_params),
+                                        C.POINTER(gq_asm_path_block), C.POINTER(gq_haplik_params),
+                                        C.POINTER(C.POINTER(gq_haplik_block))]
+        L.gq_haplik_free_block.argtypes = [C.POINTER(gq_haplik_block)]
+        L.gq_haplik_free_block.restype = None
+        L.gq_haplik_genotypes_host.argtypes = [C.c_int64] + [vp] * 6 + [C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -701,6 +741,105 @@ def asm_graphs_host_packed(packed, threads: int = 1, **params) -> AsmGraphs:
     return AsmGraphs(asm_graphs_host_call(packed, threads, **params))
 
 
+# ---- haplotype likelihoods (gq_haplik_*) ----
+HL_UNDERFLOW, HL_EMPTY = 1, 2
+
+
+def haplik_params(mismatch_probability: Optional[float] = None, open_gap_probability: Optional[float] = None,
+                  close_gap_probability: Optional[float] = None, quality_floor: Optional[float] = None) -> gq_haplik_params:
+    """gq_haplik_params: the library's defaults (e^-4, e^-6, 1 - e^-1, 6) where None."""
+    p = gq_haplik_params()
+    lib().gq_haplik_default_params(C.byref(p))
+    for name, v in (("mismatch_probability", mismatch_probability), ("open_gap_probability", open_gap_probability),
+                    ("close_gap_probability", close_gap_probability), ("quality_floor", quality_floor)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def haplik_tables(**params) -> Dict[str, np.ndarray]:
+    """gq_haplik_tables: trans (tMM tMI tMD tII tDD tIM tDM 0), match[256] and mismatch[256] by raw quality."""
+    p = haplik_params(**params)
+    t, m, x = np.zeros(8, np.float64), np.zeros(256, np.float64), np.zeros(256, np.float64)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    _check(lib().gq_haplik_tables(C.byref(p), dp(t), dp(m), dp(x)))
+    return dict(trans=t, match=m, mismatch=x)
+
+
+def haplik_pack(reads: Sequence[bytes], quals: Optional[Sequence[bytes]], haplotypes: Sequence[bytes]):
+    """Host pools and offsets of (read, qualities, haplotype) pairs, as gq_haplik_batch takes them; quals None:
+    no qualities."""
+    seq, so, sl, hap, ho, hl = pack_pairs(reads, haplotypes)
+    qual = None
+    if quals is not None:
+        if [len(q) for q in quals] != [len(r) for r in reads]:
+            raise ValueError("qualities and reads differ in length")
+        qual = np.frombuffer(b"".join(bytes(x) for x in quals) or b"\0", np.uint8)
+    return seq, so, sl, qual, hap, ho, hl
+
+
+def _haplik_args(packed):
+    seq, so, sl, qual, hap, ho, hl = packed
+    return [len(sl), seq.ctypes.data, so.ctypes.data, sl.ctypes.data, qual.ctypes.data if qual is not None else None,
+            hap.ctypes.data, ho.ctypes.data, hl.ctypes.data]
+
+
+def _haplik_pairs(out) -> Dict[str, object]:
+    """A gq_haplik_pairs block copied into numpy arrays (and freed)."""
+    try:
+        a = out.contents
+        n = int(a.n)
+        take = lambda p, dt: np.ctypeslib.as_array(p, (n,)).astype(dt, copy=True) if n else np.zeros(0, dt)  # noqa: E731
+        return dict(n=n, scaled=take(a.scaled, np.float64), log_likelihood=take(a.log_likelihood, np.float64),
+                    flags=take(a.flags, np.uint8), ms=float(a.ms), kernel_ms=float(a.kernel_ms))
+    finally:
+        lib().gq_haplik_free_pairs(out)
+
+
+def haplik_host(packed, threads: int = 1, **params) -> Dict[str, object]:
+    """gq_haplik_host over haplik_pack's arrays: the CPU twin of Context.haplik_batch."""
+    p = haplik_params(**params)
+    out = C.POINTER(gq_haplik_pairs)()
+    _check(lib().gq_haplik_host(*_haplik_args(packed), C.byref(p), int(threads), C.byref(out)))
+    return _haplik_pairs(out)
+
+
+def haplik_genotypes_host(win_read_off, hap_off, lik_off, scaled) -> Dict[str, np.ndarray]:
+    """gq_haplik_genotypes_host: gt_off, gt_log_likelihood and best_genotype of the windows."""
+    wro, ho, lo = (np.ascontiguousarray(x, np.int64) for x in (win_read_off, hap_off, lik_off))
+    sc = np.ascontiguousarray(scaled, np.float64)
+    w = len(wro) - 1
+    if w < 0 or len(ho) != w + 1 or len(lo) != w + 1:
+        raise ValueError("offset arrays of different lengths")
+    gt_off = np.zeros(w + 1, np.int64)
+    args = [w, wro.ctypes.data, ho.ctypes.data, lo.ctypes.data, sc.ctypes.data if sc.size else None, gt_off.ctypes.data]
+    _check(lib().gq_haplik_genotypes_host(*args, None, 0, None))
+    g = int(gt_off[w])
+    gl, best = np.zeros(max(g, 1), np.float64), np.zeros(max(w, 1), np.int32)
+    _check(lib().gq_haplik_genotypes_host(*args, gl.ctypes.data, g, best.ctypes.data))
+    return dict(gt_off=gt_off, gt_log_likelihood=gl[:g], best_genotype=best[:w])
+
+
+HAPLIK_BLOCK_ARRAYS = (("win_read_off", "w1"), ("win_reads", "n_reads"), ("lik_off", "w1"), ("scaled", "n_pairs"),
+                       ("log_likelihood", "n_pairs"), ("flags", "n_pairs"), ("gt_off", "w1"),
+                       ("gt_log_likelihood", "n_genotypes"), ("best_genotype", "n_windows"))
+
+
+def _haplik_block(out) -> Dict[str, object]:
+    """A gq_haplik_block copied into numpy arrays (and freed)."""
+    try:
+        b = out.contents
+        size = dict(n_windows=int(b.n_windows), n_reads=int(b.n_reads), n_pairs=int(b.n_pairs),
+                    n_genotypes=int(b.n_genotypes), w1=int(b.n_windows) + 1)
+        take = lambda p, k: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, p._type_)  # noqa: E731
+        res = {name: take(getattr(b, name), size[k]) for name, k in HAPLIK_BLOCK_ARRAYS}
+        res.update(n_windows=size["n_windows"], ms=float(b.ms), reads_ms=float(b.reads_ms), kernel_ms=float(b.kernel_ms),
+                   genotype_ms=float(b.genotype_ms))
+        return res
+    finally:
+        lib().gq_haplik_free_block(out)
+
+
 def _ptr(a) -> int:
     if isinstance(a, np.ndarray):
         return a.ctypes.data if a.size else 0
@@ -828,6 +967,36 @@ class Context:
         _check(lib().gq_asm_graphs(self.h, reads.h, dref.h, len(c), c.ctypes.data, s.ctypes.data, e.ctypes.data,
                                    C.byref(p), C.byref(out)))
         return AsmGraphs(out)
+
+    def haplik_batch(self, packed, **params) -> Dict[str, object]:
+        """gq_haplik_batch over haplik_pack's arrays: scaled, log_likelihood and flags per pair, the call's and
+        the kernel's device spans (ms)."""
+        p = haplik_params(**params)
+        out = C.POINTER(gq_haplik_pairs)()
+        _check(lib().gq_haplik_batch(self.h, *_haplik_args(packed), C.byref(p), C.byref(out)))
+        return _haplik_pairs(out)
+
+    def haplik_windows(self, reads: "DeviceReads", dref: "DeviceReference", contig, start, end, paths: Dict[str, object],
+                       k: Optional[int] = None, min_mapq: Optional[int] = None, **params) -> Dict[str, object]:
+        """gq_haplik_windows: the resident reads of the windows (gq_asm_graphs's selection for k and min_mapq)
+        against the haplotypes of `paths` (AsmGraphs.paths() over the same windows), and the windows' genotypes:
+        the block's arrays, and its spans."""
+        c, s, e = (np.ascontiguousarray(x, np.int32) for x in (contig, start, end))
+        ho, so = (np.ascontiguousarray(paths[n], np.int64) for n in ("hap_off", "hap_seq_off"))
+        bases = np.frombuffer(bytes(paths["bases"]) or b"\0", np.uint8)
+        if len(ho) != len(c) + 1:
+            raise ValueError("%d windows, paths over %d" % (len(c), len(ho) - 1))
+        pb = gq_asm_path_block()
+        pb.n_windows, pb.n_haplotypes = len(c), len(so) - 1
+        pb.hap_off = ho.ctypes.data_as(C.POINTER(C.c_int64))
+        pb.hap_seq_off = so.ctypes.data_as(C.POINTER(C.c_int64))
+        pb.bases = bases.ctypes.data_as(C.POINTER(C.c_uint8))
+        ap = asm_params(k=k, min_mapq=min_mapq)
+        p = haplik_params(**params)
+        out = C.POINTER(gq_haplik_block)()
+        _check(lib().gq_haplik_windows(self.h, reads.h, dref.h, len(c), c.ctypes.data, s.ctypes.data, e.ctypes.data,
+                                       C.byref(ap), C.byref(pb), C.byref(p), C.byref(out)))
+        return _haplik_block(out)
 
     def align_reads(self, reads: "DeviceReads", dref: "DeviceReference", pad: int = 32, all_reads: bool = False,
                     **probabilities) -> Dict[str, object]:

@@ -1008,6 +1008,112 @@ void gq_asm_free_graphs(gq_asm_graph_block *g);
 gq_status gq_asm_paths(const gq_asm_graph_block *graphs, const gq_asm_params *params, gq_asm_path_block **out);
 void gq_asm_free_paths(gq_asm_path_block *p);
 
+/* Haplotype likelihoods: every read of a window against every haplotype assembled for it (a pair-HMM
+ * forward pass), then Likelihood.likelihoodsOfGenotypes (likelihood/Likelihood.scala) with a uniform
+ * prior, in log space, over reads instead of pileup elements and over haplotypes instead of alleles
+ * (DESIGN.md "Haplotype likelihoods").
+ * Pair: a read of S bases with qualities q[1..S] against a haplotype of R bases.  Cells (s, r),
+ * s = 0..S, r = 0..R, three FP64 values M I D each.  With open = open_gap_probability and ext = 1 -
+ * close_gap_probability: tMM = 1 - (open + open), tMI = tMD = open, tII = tDD = ext, tIM = tDM = 1 -
+ * ext (trans[0..6] in that order of tMM tMI tMD tII tDD tIM tDM, trans[7] = 0).  Emission of read base
+ * s against haplotype base r: match[q] when the raw bytes are equal, else mismatch[q], where for qe =
+ * min(max(q, quality_floor), 255) match[q] = phredToSuccessProbability(qe) = 1 - 10^(-qe / 10) and
+ * mismatch[q] = (1 - match[q]) / 3.  A read without qualities (a null quality pool) has 1 -
+ * mismatch_probability and mismatch_probability / 3 for every base; mismatch_probability has no other
+ * use.  Every product and sum below is rounded on its own, in the written order (no fused multiply-add):
+ *   row 0:     M = I = 0, D(0, r) = INIT / (double)R for r = 0..R, INIT = 2^1000
+ *   column 0:  M(s, 0) = D(s, 0) = 0 for s >= 1
+ *   M(s, r) = prior(s, r) * ((M(s-1, r-1) * tMM + I(s-1, r-1) * tIM) + D(s-1, r-1) * tDM)      r >= 1
+ *   I(s, r) = M(s-1, r) * tMI + I(s-1, r) * tII                                                 r >= 0
+ *   D(s, r) = M(s, r-1) * tMD + D(s, r-1) * tDD                                                 r >= 1
+ *   sum = 0; for r = 1..R ascending: sum = sum + (M(S, r) + I(S, r))
+ * scaled = sum and log_likelihood = log(sum) - log(INIT), the natural logarithm of fdlibm (StrictMath)
+ * on both sides.  sum < DBL_MIN (zero or subnormal): log_likelihood = -infinity and the flag
+ * GQ_HL_UNDERFLOW; nothing else is done about underflow.  S == 0 or R == 0: scaled 0, -infinity and
+ * GQ_HL_EMPTY.  Device caps: S <= 512, R <= 4096 (the aligner's); a pair beyond them is GQ_E_CAPACITY
+ * naming the pair, nothing is truncated and *out is not written.  The host twin has no caps.
+ * Genotypes of a window with H haplotypes and reads 0..N-1 in list order: g runs over (i, j), i <= j,
+ * i-major;  gl(g) = 0; for n ascending: gl = gl + ((log(scaled[n][i] + scaled[n][j]) - log(INIT)) -
+ * log(2.0)).  A read whose two sums are both 0 makes the genotype -infinity.  H == 0 or N == 0: the
+ * window has no genotypes.                                                                     */
+enum { GQ_HL_UNDERFLOW = 1, GQ_HL_EMPTY = 2 };
+typedef struct {
+  double mismatch_probability;   /* e^-4: only for reads without qualities                      */
+  double open_gap_probability;   /* e^-6, below 0.5                                             */
+  double close_gap_probability;  /* 1 - e^-1                                                    */
+  double quality_floor;          /* 6: a whole number in 0 .. 255                               */
+  double reserved[4];            /* 0                                                           */
+} gq_haplik_params;
+typedef struct {
+  int64_t n;
+  double *scaled;                /* [n] the sum over row S, scaled by INIT                      */
+  double *log_likelihood;        /* [n]                                                         */
+  uint8_t *flags;                /* [n] GQ_HL_*                                                 */
+  float ms;                      /* device span of the call, copies included (0: host twin)     */
+  float kernel_ms;               /* ... of hap_forward_k alone                                  */
+  void *block_;                  /* owner of the arrays above (gq_haplik_free_pairs)            */
+} gq_haplik_pairs;
+typedef struct {
+  int64_t n_windows, n_reads, n_pairs, n_genotypes;
+  int64_t *win_read_off;         /* [n_windows + 1] into win_reads                              */
+  int64_t *win_reads;            /* [n_reads] resident read indexes, list order                 */
+  int64_t *lik_off;              /* [n_windows + 1] window w's pairs, read-major: read n of its list
+                                    against its haplotype h at lik_off[w] + n * H_w + h         */
+  double *scaled, *log_likelihood;  /* [n_pairs]                                                */
+  uint8_t *flags;                /* [n_pairs] GQ_HL_*                                           */
+  int64_t *gt_off;               /* [n_windows + 1] into gt_log_likelihood                      */
+  double *gt_log_likelihood;     /* [n_genotypes] a window's genotypes (i, j), i <= j, i-major   */
+  int32_t *best_genotype;        /* [n_windows] index within the window of the first largest
+                                    gt_log_likelihood, -1 when the window has none              */
+  float ms;                      /* device span of the call, copies included                    */
+  float reads_ms;                /* ... of finding the windows' reads                           */
+  float kernel_ms;               /* ... of hap_forward_k                                        */
+  float genotype_ms;             /* ... of the genotype kernels                                 */
+  void *block_;                  /* owner of the arrays above (gq_haplik_free_block)            */
+} gq_haplik_block;
+#ifdef __cplusplus
+static_assert(sizeof(gq_haplik_params) == 64, "gq_haplik_params layout");
+static_assert(sizeof(gq_haplik_pairs) == 48, "gq_haplik_pairs layout");
+static_assert(sizeof(gq_haplik_block) == 128, "gq_haplik_block layout");
+#endif
+void gq_haplik_default_params(gq_haplik_params *out);
+/* The tables the kernel and the twin read.  GQ_E_ARG unless every probability lies strictly inside
+ * (0, 1), open_gap_probability < 0.5 and quality_floor is a whole number in 0 .. 255.            */
+gq_status gq_haplik_tables(const gq_haplik_params *params, double trans[8], double match[256], double mismatch[256]);
+/* Pair i: seq_pool[seq_off[i], + seq_len[i]) with the qualities at the same offsets of qual_pool
+ * (null: no qualities) against hap_pool[hap_off[i], + hap_len[i]) (host arrays, copied to the
+ * device).  n == 0: GQ_OK, an empty block, no launch.                                            */
+gq_status gq_haplik_batch(gq_ctx *ctx, int64_t n, const uint8_t *seq_pool, const int64_t *seq_off,
+                          const int32_t *seq_len, const uint8_t *qual_pool, const uint8_t *hap_pool,
+                          const int64_t *hap_off, const int32_t *hap_len, const gq_haplik_params *params,
+                          gq_haplik_pairs **out);
+/* The same on the CPU (plain C++, no device, no caps), `threads` workers over the pairs (<= 1: the
+ * calling thread): the twin the GPU results are compared with.                                   */
+gq_status gq_haplik_host(int64_t n, const uint8_t *seq_pool, const int64_t *seq_off, const int32_t *seq_len,
+                         const uint8_t *qual_pool, const uint8_t *hap_pool, const int64_t *hap_off,
+                         const int32_t *hap_len, const gq_haplik_params *params, int32_t threads,
+                         gq_haplik_pairs **out);
+void gq_haplik_free_pairs(gq_haplik_pairs *p);
+/* The resident reads of each window against the haplotypes `paths` holds for it (hap_off, hap_seq_off
+ * and bases of a gq_asm_path_block over the same n_windows windows), and the windows' genotypes.  A
+ * window's reads are gq_asm_graphs's, in its list order: overlap, at least asm_params->k bases, every
+ * byte one of A C G T, mapping quality >= asm_params->min_mapq (no other field of asm_params is
+ * read; null: the defaults).  Pairs, likelihoods and genotypes are made on the device; nothing comes
+ * back to the host but the block.  GQ_E_CAPACITY names the first pair over a cap.                */
+gq_status gq_haplik_windows(gq_ctx *ctx, const gq_dev_reads *reads, const gq_reference *reference, int64_t n_windows,
+                            const int32_t *contig, const int32_t *start, const int32_t *end,
+                            const gq_asm_params *asm_params, const gq_asm_path_block *paths,
+                            const gq_haplik_params *params, gq_haplik_block **out);
+void gq_haplik_free_block(gq_haplik_block *b);
+/* Host only: the genotype step.  Window w has the reads win_read_off[w + 1] - win_read_off[w], the
+ * haplotypes hap_off[w + 1] - hap_off[w] and its pairs' scaled values at lik_off[w], read-major.
+ * gt_off[n_windows + 1] is always written; gt_log_likelihood (room for gt_capacity values) and
+ * best_genotype[n_windows] when gt_log_likelihood is not null (null: the offsets alone, to size it).
+ * GQ_E_ARG when gt_capacity is less than gt_off[n_windows].                                      */
+gq_status gq_haplik_genotypes_host(int64_t n_windows, const int64_t *win_read_off, const int64_t *hap_off,
+                                   const int64_t *lik_off, const double *scaled, int64_t *gt_off,
+                                   double *gt_log_likelihood, int64_t gt_capacity, int32_t *best_genotype);
+
 #ifdef __cplusplus
 }
 #endif
