@@ -100,6 +100,82 @@ def planted_pairs(n, seed, max_s=150, max_r=220, max_indel=30):
     return out
 
 
+def tb_bytes(S, R, lim):
+    """The bytes of a pair's traceback (lim: native.align_limits()): a byte a lane and step up to 4 rows a
+    lane, a halfword past that."""
+    rpl = -(-S // lim["lanes"])
+    nl = -(-S // rpl)
+    return nl * (R + nl) * (1 if rpl <= 4 else 2)
+
+
+def largest_r_in_lds(S, lim):
+    R = 0
+    while tb_bytes(S, R + 1, lim) <= lim["lds_bytes"]:
+        R += 1
+    return R
+
+
+LONG_GAP_S = (300, 512)  # both on the wide traceback format (more than 4 rows a lane)
+
+
+def long_gap_pairs(lim, seed=31):
+    """One planted gap a pair, on the wide format, with the traceback in LDS and in global scratch:
+    (S, sequence, reference, op, run length).  Per S: an insertion of S - R bases with R the largest that
+    keeps the traceback in LDS, the same with R one more (global scratch), and, with R past S, a deletion
+    of 70 or more bases (across a multiple of 64 columns) and an insertion of 40 or more (5 lanes or more)."""
+    rng = random.Random(seed)
+    seq_of = lambda n: bytes(rng.choice(b"ACGT") for _ in range(n))  # noqa: E731
+    out = []
+    for S in LONG_GAP_S:
+        rpl = -(-S // lim["lanes"])
+        assert rpl > 4
+        fit = largest_r_in_lds(S, lim)
+        assert 0 < fit < S - 40
+        for R_ in (fit, fit + 1):
+            ref = seq_of(R_)
+            at = R_ // 2
+            out.append((S, ref[:at] + seq_of(S - R_) + ref[at:], ref, "I", S - R_))
+        gone = 70 + S // 100  # 73 and 75 bases
+        ref = seq_of(S + gone + 50)
+        at = 64 * (S // 128) - 30
+        assert (20 + at) // 64 < (20 + at + gone) // 64  # the deleted reference columns hold a multiple of 64
+        window = ref[20:20 + S + gone]
+        out.append((S, window[:at] + window[at + gone:], ref, "D", gone))
+        grown = 40 + S // 64  # 44 and 48 bases: 8 lanes of 5 rows, 6 of 8
+        assert grown >= 40 and grown // rpl >= 5
+        ref = seq_of(S + 30)
+        window = ref[10:10 + S - grown]
+        at = len(window) // 3
+        out.append((S, window[:at] + seq_of(grown) + window[at:], ref, "I", grown))
+    for S, seq, ref, op, n in out:
+        assert len(seq) == S
+        inside = tb_bytes(S, len(ref), lim) <= lim["lds_bytes"]
+        assert inside == (len(ref) == largest_r_in_lds(S, lim))
+    return out
+
+
+def planted_run(words, op, n):
+    """Whether a CIGAR's BAM words hold a run of exactly n of op (I or D) and no other gap that long."""
+    code = {"I": 1, "D": 2}[op]
+    runs = [int(w) >> 4 for w in words if int(w) & 15 == code]
+    others = [int(w) >> 4 for w in words if int(w) & 15 in (1, 2) and int(w) & 15 != code]
+    return runs.count(n) == 1 and max(runs) == n and all(x < n for x in others)
+
+
+TIE_S = (65, 130, 300, 512)
+
+
+def tie_pairs():
+    """Periodic and homopolymer pairs: every second (every) column of row S from S on ends an alignment of
+    S matches, all of one score; the first of them, column S, is the end.  R is S + 64 and S + 65."""
+    out = []
+    for S in TIE_S:
+        out.append(((b"AC" * S)[:S], b"AC" * ((S + 65) // 2)))
+        out.append(((b"AC" * S)[:S], (b"AC" * S)[:S + 65]))
+        out.append((b"A" * S, b"A" * (S + 64)))
+    return out
+
+
 def rows_of(res):
     """(ref_start, ref_end, score bits, score_int, CIGAR words) per pair of a library result."""
     off = res["cigar_off"]

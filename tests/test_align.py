@@ -115,6 +115,46 @@ def test_host_random_two_letter_pairs(table):
     check_host(A.random_pairs(200, 40, 60, b"AC", seed=11), table)
 
 
+def test_host_long_planted_gaps(table):
+    """align_cases.long_gap_pairs: the planted D and I runs are in the twin's CIGARs at their planted
+    lengths; the twin against the restatement at S = 300 (S = 512 takes the restatement too long)."""
+    lim = native.align_limits()
+    cases = A.long_gap_pairs(lim)
+    assert sorted({S for S, *_ in cases}) == list(A.LONG_GAP_S)
+    res = native.align_host(native.pack_pairs([s for _, s, *_ in cases], [r for _, _, r, *_ in cases]))
+    off = res["cigar_off"]
+    kinds = set()
+    for i, (S, seq, ref, op, n) in enumerate(cases):
+        assert A.planted_run(res["cigar"][off[i]:off[i + 1]], op, n), (i, S, op, n, align.rows(res)[i]["cigar"])
+        wide = -(-S // lim["lanes"]) > 4
+        kinds.add((S, op, A.tb_bytes(S, len(ref), lim) <= lim["lds_bytes"]))
+        assert wide and n >= (70 if op == "D" else 40)
+    for S in A.LONG_GAP_S:  # per S: an insertion with the traceback in LDS, a deletion and an insertion outside it
+        assert {(S, "I", True), (S, "I", False), (S, "D", False)} <= kinds
+    check_host([(seq, ref) for S, seq, ref, _, _ in cases if S == 300], table)
+
+
+def test_host_ties_along_the_last_row(table):
+    """align_cases.tie_pairs: the sequence matches the reference at every second (every) column from S
+    on, all ends of one score; the end is the first of them.  Restated here from the rule itself (a run
+    of S matches from column 0 costs the least any alignment of S bases can, and column S is the first
+    that can end one), and compared with the restatement up to S = 130."""
+    pairs = A.tie_pairs()
+    assert sorted({len(s) for s, _ in pairs}) == list(A.TIE_S) and all(len(r) - len(s) in (64, 65) for s, r in pairs)
+    res = native.align_host(native.pack_pairs([s for s, _ in pairs], [r for _, r in pairs]))
+    rows = A.rows_of(res)
+    for i, (s, r) in enumerate(pairs):
+        S = len(s)
+        assert sum(1 for e in range(S, len(r) + 1) if r[e - S:e] == s) >= 32  # the tied ends
+        want = 0.0
+        for x in range(S):
+            want = want + table[(16 if x == S - 1 else 0) + 4 * (3 if x else 0) + R.MATCH]
+        row = rows[i]
+        assert row[:2] == (0, S) and row[4] == [(S << 4) | 7], (i, row[:2])
+        assert row[2] == int(np.float64(want).view(np.uint64))
+    check_host([p for p in pairs if len(p[0]) <= 130], table)
+
+
 def test_host_empty_batch():
     res = native.align_host(native.pack_pairs([], []))
     assert res["n"] == 0 and list(res["cigar_off"]) == [0] and len(res["cigar"]) == 0

@@ -47,17 +47,7 @@ def check(ctx, pairs, **probabilities):
     return got
 
 
-def tb_bytes(S, R, lim):
-    rpl = -(-S // lim["lanes"])
-    nl = -(-S // rpl)
-    return nl * (R + nl) * (1 if rpl <= 4 else 2)
-
-
-def largest_r_in_lds(S, lim):
-    R = 0
-    while tb_bytes(S, R + 1, lim) <= lim["lds_bytes"]:
-        R += 1
-    return R
+tb_bytes, largest_r_in_lds = A.tb_bytes, A.largest_r_in_lds
 
 
 def test_suite_and_tie_cases(gpu_ctx):
@@ -129,17 +119,16 @@ def test_capacity_errors(gpu_ctx):
     assert rc == native.E_CAPACITY and not out
 
 
-def test_batch_shapes(gpu_ctx):
-    lim = native.align_limits()
-    res = gpu_ctx.align_batch(native.pack_pairs([], []))
-    assert res["n"] == 0 and res["launches"] == 0 and list(res["cigar_off"]) == [0]
+def batch_shape_pairs(lim):
+    """(a batch of one, a batch of two with an empty sequence, 257 pairs of mixed lengths with empty and
+    cap-sized pairs between them)."""
     rng = random.Random(24)
     ref = rand_seq(rng, 90)
-    check(gpu_ctx, [(read_of(rng, ref, 60), ref)])
-    check(gpu_ctx, [(read_of(rng, ref, 60), ref), (b"", ref)])
+    one = [(read_of(rng, ref, 60), ref)]
+    two = [(read_of(rng, ref, 60), ref), (b"", ref)]
     big = rand_seq(rng, lim["max_r"])
     pairs = []
-    for i in range(257):  # mixed lengths, empty and cap-sized pairs between them
+    for i in range(257):
         if i % 100 == 50:
             pairs.append((read_of(rng, big, lim["max_s"]), big))
         elif i % 9 == 4:
@@ -147,7 +136,57 @@ def test_batch_shapes(gpu_ctx):
         else:
             r = rand_seq(rng, rng.randint(0, 300), b"AC" if i % 2 else b"ACGT")
             pairs.append((read_of(rng, r, rng.randint(0, 200)), r))
+    return one, two, pairs
+
+
+def test_batch_shapes(gpu_ctx):
+    lim = native.align_limits()
+    res = gpu_ctx.align_batch(native.pack_pairs([], []))
+    assert res["n"] == 0 and res["launches"] == 0 and list(res["cigar_off"]) == [0]
+    one, two, pairs = batch_shape_pairs(lim)
+    check(gpu_ctx, one)
+    check(gpu_ctx, two)
     check(gpu_ctx, pairs)
+
+
+def test_scratch_chunking_over_a_mixed_batch(gpu_ctx, monkeypatch):
+    """test_batch_shapes' 257 pairs under the smallest scratch limit: a launch's chunk holds pairs with the
+    traceback in LDS (no traceback region), pairs with it in global scratch and empty pairs, so a pair's
+    scratch offset and its traceback region both count."""
+    lim = native.align_limits()
+    _, _, pairs = batch_shape_pairs(lim)
+    inside = [tb_bytes(len(s), len(r), lim) <= lim["lds_bytes"] for s, r in pairs if s]
+    assert 20 < sum(inside) < len(inside) - 20 and sum(1 for s, _ in pairs if not s) > 20
+    monkeypatch.delenv("GQ_ALIGN_SCRATCH_BYTES", raising=False)
+    whole = check(gpu_ctx, pairs)
+    monkeypatch.setenv("GQ_ALIGN_SCRATCH_BYTES", "1")
+    cut = check(gpu_ctx, pairs)
+    assert cut["launches"] > 1 and whole["launches"] == 1
+    A.same_blocks(cut, whole)
+
+
+def test_long_gaps_on_the_wide_traceback(gpu_ctx):
+    """align_cases.long_gap_pairs: at S = 300 and 512 (a halfword a lane and step), one insertion run of 40
+    or more bases (5 lanes and more) or one deletion run of 70 or more (across a 64-column chunk reload),
+    with the traceback in LDS and in global scratch."""
+    lim = native.align_limits()
+    cases = A.long_gap_pairs(lim)
+    got = check(gpu_ctx, [(seq, ref) for _, seq, ref, _, _ in cases])
+    off = got["cigar_off"]
+    for i, (S, seq, ref, op, n) in enumerate(cases):
+        assert A.planted_run(got["cigar"][off[i]:off[i + 1]], op, n), (i, S, op, n)
+    assert {(tb_bytes(S, len(ref), lim) <= lim["lds_bytes"], op) for S, _, ref, op, _ in cases} == {
+        (True, "I"), (False, "I"), (False, "D")}
+
+
+def test_ties_along_the_last_row(gpu_ctx):
+    """align_cases.tie_pairs: 32 and more equal-scoring ends along row S at S = 65, 130, 300, 512, so the
+    ends lie in the last lane's registers over several chunks; the end is the first, column S."""
+    pairs = A.tie_pairs()
+    got = check(gpu_ctx, pairs)
+    assert [int(x) for x in got["ref_end"]] == [len(s) for s, _ in pairs] and not got["ref_start"].any()
+    for p in pairs[::3]:  # each as a batch of one
+        check(gpu_ctx, [p])
 
 
 @pytest.fixture(scope="module")

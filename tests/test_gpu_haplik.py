@@ -33,6 +33,45 @@ def test_row_ownership_and_chunk_boundaries(gpu_ctx):
     assert not got["flags"].any() and np.isfinite(got["log_likelihood"]).all() and got["kernel_ms"] > 0
 
 
+def test_every_row_count(gpu_ctx):
+    """2 to 8 rows a lane, S on each side of every step (127 .. 129, 191 .. 193, ..., 511, 512), against
+    R = 40 and R = 3: each unrolled `k < rpl` row and its carry to the next."""
+    pairs = H.row_count_pairs(H.rng(17))
+    assert {-(-len(p[0]) // 64) for p in pairs} == set(range(2, 9))
+    got = check(gpu_ctx, pairs)
+    assert not got["flags"].any()
+    check(gpu_ctx, pairs, with_quals=False)
+
+
+def test_ragged_last_lanes_and_chunk_reloads(gpu_ctx):
+    """Every S from 1 to 130 against R = 70; S = 1 against R at the chunk edges and the cap; S = 300 (60
+    lanes) against R = 1, 4, 59, 60, 61, 68, 4096, where R + 60 steps end at and next to a chunk reload."""
+    pairs = H.ragged_pairs(H.rng(18))
+    assert len(pairs) == 130 + 7 + 7
+    got = check(gpu_ctx, pairs)
+    assert not got["flags"].any() and np.isfinite(got["log_likelihood"]).all()
+
+
+def test_byte_values(gpu_ctx):
+    """Quality bytes over 0 .. 255, the byte 0 as a base on both sides (a match) and on one (pad rows and
+    columns count for nothing), bases of 128 and more."""
+    pairs = H.byte_value_pairs(H.rng(19))
+    got = check(gpu_ctx, pairs)
+    assert not got["flags"].any() and got["scaled"][3] > 1e20 * got["scaled"][4] > 0
+    check(gpu_ctx, pairs, with_quals=False)
+    check(gpu_ctx, pairs, quality_floor=0)
+    check(gpu_ctx, pairs, quality_floor=255)
+
+
+def test_pairs_that_share_bytes(gpu_ctx):
+    """Offset arrays as the window path makes them: shared read and haplotype bytes, descending offsets,
+    partial overlaps."""
+    packed = H.shared_bytes_pack(H.rng(20))
+    got = gpu_ctx.haplik_batch(packed)
+    H.same_pairs(got, native.haplik_host(packed, threads=4))
+    assert got["n"] == 32 and not got["flags"].any()
+
+
 def test_qualities(gpu_ctx):
     pairs = H.quality_pairs(H.rng(12))
     floored, top, mixed = check(gpu_ctx, pairs)["scaled"]

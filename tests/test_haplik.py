@@ -77,6 +77,127 @@ def test_twin_on_random_pairs(tables):
     check_twin(H.random_pairs(H.rng(3), 200), tables)
 
 
+def test_twin_at_every_row_count(tables):
+    """S on each side of every rows-per-lane step of the device kernel, against R = 40 and R = 3."""
+    pairs = H.row_count_pairs(H.rng(7))
+    assert {-(-len(s) // 64) for s, _, _ in pairs} == set(range(2, 9))
+    assert {len(s) for s, _, _ in pairs} >= {127, 128, 129, 255, 256, 257, 319, 320, 321, 383, 384, 385, 511, 512}
+    assert {len(h) for _, _, h in pairs} == {40, 3}
+    check_twin(pairs, tables)
+
+
+def test_twin_on_byte_values(tables):
+    """Quality bytes over 0 .. 255, the byte 0 as a base, bases of 128 and more."""
+    pairs = H.byte_value_pairs(H.rng(8))
+    assert set(pairs[0][1]) == set(range(256)) and set(pairs[2][1]) == {255}
+    got = check_twin(pairs, tables)
+    assert not got["flags"].any()
+    # \0 against \0 scores as a match: far above the same read against a haplotype without \0
+    assert got["scaled"][3] > 1e20 * got["scaled"][4] > 0
+    same = native.haplik_host(H.pack([(b"A" * 70, pairs[3][1], b"A" * 50)]))["scaled"][0]
+    assert got["scaled"][3].tobytes() == same.tobytes()  # only equality of bytes counts, not their value
+    check_twin(pairs[3:], tables, with_quals=False)
+
+
+def test_ragged_builder_shapes():
+    pairs = H.ragged_pairs(H.rng(9))
+    assert [len(s) for s, _, _ in pairs[:130]] == list(range(1, 131)) and {len(h) for _, _, h in pairs[:130]} == {70}
+    lanes = lambda s: -(-s // -(-s // 64))  # noqa: E731
+    assert {lanes(len(s)) for s, _, _ in pairs[:130]} == set(range(1, 65))
+    assert [(len(s), len(h)) for s, _, h in pairs[130:]] == (
+        [(1, r) for r in (63, 64, 65, 127, 128, 129, 4096)] + [(300, r) for r in (1, 4, 59, 60, 61, 68, 4096)])
+    assert lanes(300) == 60 and (4 + 60) % 64 == 0 and (68 + 60) % 64 == 0
+
+
+def test_twin_on_shared_bytes():
+    """The hand-made offset arrays (shared, descending, overlapping) against each pair packed on its own."""
+    packed = H.shared_bytes_pack(H.rng(10))
+    seq, so, sl, qual, hap, ho, hl = packed
+    assert len(set(so.tolist())) < len(so) and len(set(ho.tolist())) < len(ho) and (np.diff(so) < 0).any() and (np.diff(ho) < 0).any()
+    spans = sorted(set(zip(so.tolist(), (so + sl).tolist())))
+    assert any(a < c < b < d for a, b in spans for c, d in spans)  # a partial overlap
+    alone = [(seq[a:a + n].tobytes(), qual[a:a + n].tobytes(), hap[b:b + m].tobytes()) for a, n, b, m in zip(so, sl, ho, hl)]
+    H.same_pairs(native.haplik_host(packed, threads=3), native.haplik_host(H.pack(alone)))
+
+
+# ---- the window cases of test_gpu_haplik_windows.py: each builder's preconditions, from the twin alone ----
+def test_window_case_preconditions():
+    case = H.order_case()
+    H.order_preconditions(case, H.twin_block(case))
+    case, kinds = H.empty_case()
+    assert set(kinds) == {H.FULL} | set(H.EMPTY_KINDS)
+    H.empty_preconditions(case, kinds, H.twin_block(case))
+    case = H.workgroup_case()
+    counts = H.workgroup_preconditions(case, H.twin_block(case))
+    assert counts == dict(windows=302, pairs=1980, genotypes=1500)
+    H.tie_preconditions(H.twin_block(H.tie_case()))
+    zero, sub, normal = H.underflow_lengths()
+    assert zero and sub and normal and max(zero + sub + normal) <= 512  # both underflow kinds are found
+    H.underflow_preconditions(H.twin_block(H.underflow_case(), **H.STEEP))
+    first, last = H.long_read_preconditions(H.long_read_case())
+    assert first == 2 and last - first > 256 and H.long_read_preconditions(H.long_read_case(False)) == []
+    assert 4097 in np.diff(H.long_hap_case()["paths"]["hap_seq_off"])
+    assert list(np.diff(H.twin_block(H.long_hap_case(False))["win_read_off"])) == [2, 0, 2]
+    case, low = H.selection_case()
+    window, reads = case["windows"][0], case["reads"]
+    strict, loose = H.selected(reads, window, case["k"], H.SELECTION_MAPQ), H.selected(reads, window, case["k"], 0)
+    assert len(strict) == 3 and loose == sorted(strict + [low])
+    left_out = [r for i, r in enumerate(reads) if i not in loose]
+    assert all(r["start"] < window[2] + 1 and r["start"] + len(r["seq"]) > window[1] for r in left_out)
+    assert sorted(("short" if len(r["seq"]) < case["k"] else "N" if b"N" in r["seq"] else "touches")
+                  for r in left_out) == ["N", "short", "touches"]
+    assert [r["start"] for r in left_out if b"N" not in r["seq"] and len(r["seq"]) >= case["k"]] == [window[2]]
+
+
+def test_window_comparison_discriminates():
+    """same_block fails on an expected side with two genotypes of a window swapped, a window's n x H block
+    transposed, or lik_off shifted by a window: the cases tell a subtly wrong kernel from a right one."""
+    def fails(want, change):
+        bad = {k: np.array(v, copy=True) for k, v in want.items()}
+        change(bad)
+        with pytest.raises(AssertionError):
+            H.same_block(bad, want)
+
+    def swap_genotypes(w, a, b):
+        def change(blk):
+            g = blk["gt_log_likelihood"]
+            at = int(blk["gt_off"][w])
+            g[at + a], g[at + b] = g[at + b], g[at + a]
+        return change
+
+    def transpose(w, case):
+        def change(blk):
+            a, b = int(blk["lik_off"][w]), int(blk["lik_off"][w + 1])
+            h = int(np.diff(case["paths"]["hap_off"])[w])
+            for key in ("scaled", "log_likelihood"):
+                blk[key][a:b] = blk[key][a:b].reshape(-1, h).T.ravel()
+        return change
+
+    def shift_lik_off(blk):
+        blk["lik_off"][:-1] = blk["lik_off"][1:]
+
+    case = H.order_case()
+    want = H.twin_block(case)
+    H.same_block({k: np.array(v, copy=True) for k, v in want.items()}, want)
+    for w, h in enumerate(H.ORDER_H):
+        if h >= 3:  # every two genotypes of such a window differ
+            fails(want, swap_genotypes(w, 1, h))  # (0, 1) and (1, 1): a swapped (i, j) walk
+            fails(want, swap_genotypes(w, h * (h + 1) // 2 - 2, h * (h + 1) // 2 - 1))
+        if h >= 2 and np.diff(want["win_read_off"])[w] >= 2:
+            fails(want, transpose(w, case))
+    fails(want, shift_lik_off)
+    case, kinds = H.empty_case()
+    want = H.twin_block(case)
+    fails(want, shift_lik_off)
+    full = [w for w, k in enumerate(kinds) if k == H.FULL and np.diff(case["paths"]["hap_off"])[w] >= 2]
+    fails(want, swap_genotypes(full[0], 0, 1))
+    want = H.twin_block(H.tie_case())
+    fails(want, swap_genotypes(1, 0, 3))
+    want = H.twin_block(H.underflow_case(), **H.STEEP)
+    fails(want, swap_genotypes(1, 0, 2))
+    fails(want, shift_lik_off)
+
+
 def test_underflow(tables):
     # the default gap probabilities let a run of insertions through at e^-1 a base: no underflow within the cap
     for q in (60, 93):
