@@ -1504,13 +1504,88 @@ def haplotype_likelihoods_main(argv: Sequence[str]) -> int:
     return 0
 
 
+def germline_assembly_main(argv: Sequence[str]) -> int:
+    """germline-assembly: haplotype-likelihoods' pipeline, then the variant events the aligned haplotypes
+    carry with their genotype likelihoods marginalised over haplotypes (gq_hapvar_windows), as VCF."""
+    import os
+    from . import assemble, variants_assembly
+    from .reference import ReferenceGenome
+    p = argparse.ArgumentParser(prog="germline-assembly",
+                                description="germline variant calls from the assembled haplotypes of each window")
+    p.add_argument("--reads", required=True, help="Aligned reads")
+    p.add_argument("--reference-fasta", required=True, help="Local path to a reference FASTA file")
+    p.add_argument("--loci", default="all", help="Loci to cut into windows (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--out", required=True, help="Output VCF path (must not exist)")
+    p.add_argument("--out-events", default="", help="Also write one TSV row per event of every window")
+    p.add_argument("--min-qual", type=float, default=0.0, help="Only calls of at least this QUAL")
+    p.add_argument("--emit-all-events", action="store_true", help="Also write events whose best genotype is 0/0")
+    p.add_argument("--sample", default="sample", help="Name of the VCF's sample column")
+    p.add_argument("--kmer-size", type=int, default=25)
+    p.add_argument("--min-occurrence", type=int, default=2, help="Occurrences a k-mer needs to be a node")
+    p.add_argument("--window-size", type=int, default=200)
+    p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
+    p.add_argument("--max-paths", type=int, default=10)
+    p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--quality-floor", type=int, default=None, help="Base qualities below it count as it (6)")
+    p.add_argument("--mismatch-probability", type=float, default=None, help="For reads without qualities")
+    p.add_argument("--open-gap-probability", type=float, default=None)
+    p.add_argument("--close-gap-probability", type=float, default=None)
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    args = p.parse_args(argv)
+    single_process_only("germline-assembly")
+    for path in (args.out, args.out_events):
+        if path and os.path.lexists(path):
+            raise FileExistsError("Output path %s already exists" % path)
+    clock = StageClock()
+    # the reads as stored, as assemble-windows loads them
+    load_args = argparse.Namespace(reference_fasta="", recompute_md_tags=False, device=args.device)
+    ctx, (rs,) = load_product_reads(load_args, InputFilters.make(mapped=True, non_duplicate=True), args.reads)
+    if ctx is None:
+        ctx = native.Context(args.device)
+    dr = device_reads(ctx, rs)
+    clock.mark("load_reads")
+    names = list(rs.contig_names)
+    contigs = ReferenceGenome.load_fasta(args.reference_fasta).for_contigs(names)
+    dref = ctx.upload_reference(contigs)
+    clock.mark("load_reference")
+    loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
+    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                   args.window_step or None, args.kmer_size)
+    info: dict = {}
+    try:
+        rows, _, _ = variants_assembly.call_windows(
+            ctx, dr, dref, windows, names, dict(zip(names, contigs)), k=args.kmer_size,
+            min_occurrence=args.min_occurrence, max_paths=args.max_paths, min_mapq=args.min_mapq, info=info,
+            quality_floor=args.quality_floor, mismatch_probability=args.mismatch_probability,
+            open_gap_probability=args.open_gap_probability, close_gap_probability=args.close_gap_probability)
+    finally:
+        dref.free()
+    clock.mark("call")
+    calls = variants_assembly.select_calls(rows, names, emit_all=args.emit_all_events, min_qual=args.min_qual)
+    with open(args.out, "w") as fh:
+        fh.write(variants_assembly.vcf_text(calls, args.sample, dict(rs.contig_lengths_map)))
+    if args.out_events:
+        with open(args.out_events, "w") as fh:
+            fh.write(variants_assembly.EVENT_HEADER + "\n")
+            fh.writelines(l + "\n" for l in variants_assembly.event_tsv_lines(rows))
+    clock.mark("write")
+    print("%d windows, %d haplotypes (%d not usable), %d events (%d indels dropped at a window's edge, %d windows "
+          "over the event cap); wrote %d calls." %
+          (len(windows), info["n_haplotypes"], info["n_unusable"], info["n_events"], info["n_edge_dropped"],
+           info["n_capped_windows"], len(calls)), file=sys.stderr)
+    clock.report(windows=len(windows), graphs_ms=info["graphs_ms"], paths_ms=info["paths_ms"], align_ms=info["align_ms"],
+                 haplik_ms=info["haplik_ms"], hapvar_ms=info["hapvar_ms"], events_ms=info["events_ms"],
+                 marginal_ms=info["marginal_ms"])
+    return 0
+
+
 COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": somatic_standard_main,
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
             "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main,
             "realign-reads": realign_reads_main, "assemble-windows": assemble_windows_main,
-            "haplotype-likelihoods": haplotype_likelihoods_main}
+            "haplotype-likelihoods": haplotype_likelihoods_main, "germline-assembly": germline_assembly_main}
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:

@@ -324,6 +324,25 @@ class gq_haplik_block(C.Structure):
                 ("kernel_ms", C.c_float), ("genotype_ms", C.c_float), ("block_", C.c_void_p)]
 
 
+class gq_hapvar_input(C.Structure):
+    _fields_ = [("n_windows", C.c_int64), ("n_haplotypes", C.c_int64), ("n_align", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("win_start", "ref_pool", "ref_off", "win_len", "hap_off", "hap_seq_off", "bases",
+                                  "hap_align", "ref_start", "ref_end", "cigar_off", "cigar", "win_read_off", "lik_off",
+                                  "scaled")]
+
+
+class gq_hapvar_block(C.Structure):
+    _fields_ = [("n_windows", C.c_int64), ("n_events", C.c_int64), ("n_haplotypes", C.c_int64),
+                ("n_alt_bases", C.c_int64), ("ev_off", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_int64)),
+                ("kind", C.POINTER(C.c_uint8)), ("ref_len", C.POINTER(C.c_int32)), ("alt_off", C.POINTER(C.c_int64)),
+                ("alt_len", C.POINTER(C.c_int32)), ("alt_bases", C.POINTER(C.c_uint8)),
+                ("carriers", C.POINTER(C.c_uint64)), ("gl", C.POINTER(C.c_double)), ("best", C.POINTER(C.c_int32)),
+                ("ad_ref", C.POINTER(C.c_int32)), ("ad_alt", C.POINTER(C.c_int32)), ("dp", C.POINTER(C.c_int32)),
+                ("ev_flags", C.POINTER(C.c_uint8)), ("hap_flags", C.POINTER(C.c_uint8)),
+                ("win_flags", C.POINTER(C.c_uint8)), ("n_edge_dropped", C.c_int64), ("ms", C.c_float),
+                ("events_ms", C.c_float), ("marginal_ms", C.c_float), ("reserved", C.c_int32), ("block_", C.c_void_p)]
+
+
 # gq_pileup_elements.elem_kind (PileupElement.alignment)
 ELEMENT_KINDS = ("Match", "Mismatch", "Insertion", "Deletion", "MidDeletion", "Clipped")
 
@@ -348,7 +367,8 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_asm_default_params", "gq_asm_limits", "gq_asm_graphs", "gq_asm_graphs_host", "gq_asm_free_graphs",
             "gq_asm_paths", "gq_asm_free_paths",
             "gq_haplik_default_params", "gq_haplik_tables", "gq_haplik_batch", "gq_haplik_host", "gq_haplik_free_pairs",
-            "gq_haplik_windows", "gq_haplik_free_block", "gq_haplik_genotypes_host")
+            "gq_haplik_windows", "gq_haplik_free_block", "gq_haplik_genotypes_host",
+            "gq_hapvar_limits", "gq_hapvar_windows", "gq_hapvar_host", "gq_hapvar_free_block")
 
 
 def lib():
@@ -528,6 +548,14 @@ def lib():
         L.gq_haplik_free_block.argtypes = [C.POINTER(gq_haplik_block)]
         L.gq_haplik_free_block.restype = None
         L.gq_haplik_genotypes_host.argtypes = [C.c_int64] + [vp] * 6 + [C.c_int64, vp]
+        L.gq_hapvar_limits.argtypes = [C.POINTER(C.c_int32)]
+        L.gq_hapvar_limits.restype = None
+        L.gq_hapvar_windows.argtypes = [vp, C.POINTER(gq_hapvar_input), C.POINTER(C.POINTER(gq_hapvar_block))]
+        L.gq_hapvar_windows.restype = C.c_int
+        L.gq_hapvar_host.argtypes = [C.POINTER(gq_hapvar_input), C.c_int32, C.POINTER(C.POINTER(gq_hapvar_block))]
+        L.gq_hapvar_host.restype = C.c_int
+        L.gq_hapvar_free_block.argtypes = [C.POINTER(gq_hapvar_block)]
+        L.gq_hapvar_free_block.restype = None
         _lib = L
     return _lib
 
@@ -840,6 +868,77 @@ def _haplik_block(out) -> Dict[str, object]:
         lib().gq_haplik_free_block(out)
 
 
+# ---- variants from assembled haplotypes (gq_hapvar_*) ----
+HV_SNV, HV_INS, HV_DEL = 0, 1, 2
+HV_KINDS = ("SNV", "INS", "DEL")
+HV_HAP_UNALIGNED, HV_HAP_PARTIAL = 1, 2
+HV_EDGE_DROPPED, HV_TOO_MANY_EVENTS = 1, 2
+HV_NO_REF_SIDE = 1
+HAPVAR_INPUT_ARRAYS = (("win_start", np.int32), ("ref_pool", np.uint8), ("ref_off", np.int64), ("win_len", np.int32),
+                       ("hap_off", np.int64), ("hap_seq_off", np.int64), ("bases", np.uint8), ("hap_align", np.int64),
+                       ("ref_start", np.int32), ("ref_end", np.int32), ("cigar_off", np.int64), ("cigar", np.uint32),
+                       ("win_read_off", np.int64), ("lik_off", np.int64), ("scaled", np.float64))
+HAPVAR_BLOCK_ARRAYS = (("ev_off", "w1"), ("pos", "e"), ("kind", "e"), ("ref_len", "e"), ("alt_off", "e"), ("alt_len", "e"),
+                       ("alt_bases", "a"), ("carriers", "e"), ("gl", "e3"), ("best", "e"), ("ad_ref", "e"), ("ad_alt", "e"),
+                       ("dp", "e"), ("ev_flags", "e"), ("hap_flags", "h"), ("win_flags", "w"))
+
+
+def hapvar_limits() -> Dict[str, int]:
+    """gq_hapvar_limits: the haplotypes a window may have, the raw-event cap and the kernels' constants."""
+    v = (C.c_int32 * 8)()
+    lib().gq_hapvar_limits(v)
+    return dict(max_haplotypes=v[0], max_raw_events=v[1], sort_threads=v[2], lds_bytes=v[3], reads_per_pass=v[4])
+
+
+def hapvar_pack(win_start, window_refs, paths: Dict[str, object], hap_align, alignments: Optional[Dict[str, object]],
+                lik: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The arrays of a gq_hapvar_input.  window_refs: the windows' reference bytes (None: none); paths: hap_off,
+    hap_seq_off, bases; hap_align: per haplotype an index into `alignments` (ref_start, ref_end, cigar_off,
+    cigar; None: no alignments) or -1; lik: win_read_off, lik_off, scaled."""
+    ref_off, win_len, at = [], [], 0
+    for r in window_refs:
+        ref_off.append(-1 if r is None else at)
+        win_len.append(0 if r is None else len(r))
+        at += 0 if r is None else len(r)
+    al = alignments or dict(ref_start=[], ref_end=[], cigar_off=[0], cigar=[])
+    raw = dict(win_start=win_start, ref_pool=np.frombuffer(b"".join(bytes(r) for r in window_refs if r is not None), np.uint8),
+               ref_off=ref_off, win_len=win_len, hap_off=paths["hap_off"], hap_seq_off=paths["hap_seq_off"],
+               bases=np.frombuffer(bytes(paths["bases"]), np.uint8), hap_align=hap_align, ref_start=al["ref_start"],
+               ref_end=al["ref_end"], cigar_off=al["cigar_off"], cigar=al["cigar"], win_read_off=lik["win_read_off"],
+               lik_off=lik["lik_off"], scaled=lik["scaled"])
+    return {n: np.ascontiguousarray(raw[n], dt) for n, dt in HAPVAR_INPUT_ARRAYS}
+
+
+def hapvar_input(packed: Dict[str, np.ndarray]) -> gq_hapvar_input:
+    """The struct over hapvar_pack's arrays (which the caller keeps alive)."""
+    s = gq_hapvar_input(len(packed["win_start"]), len(packed["hap_seq_off"]) - 1, len(packed["ref_start"]))
+    for n, _ in HAPVAR_INPUT_ARRAYS:
+        setattr(s, n, packed[n].ctypes.data if packed[n].size else None)
+    return s
+
+
+def _hapvar_block(out) -> Dict[str, object]:
+    """A gq_hapvar_block copied into numpy arrays (and freed)."""
+    try:
+        b = out.contents
+        size = dict(w=int(b.n_windows), w1=int(b.n_windows) + 1, e=int(b.n_events), e3=3 * int(b.n_events),
+                    h=int(b.n_haplotypes), a=int(b.n_alt_bases))
+        take = lambda p, k: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, p._type_)  # noqa: E731
+        res = {name: take(getattr(b, name), size[k]) for name, k in HAPVAR_BLOCK_ARRAYS}
+        res.update(n_windows=size["w"], n_edge_dropped=int(b.n_edge_dropped), ms=float(b.ms),
+                   events_ms=float(b.events_ms), marginal_ms=float(b.marginal_ms))
+        return res
+    finally:
+        lib().gq_hapvar_free_block(out)
+
+
+def hapvar_host(packed: Dict[str, np.ndarray], threads: int = 1) -> Dict[str, object]:
+    """gq_hapvar_host over hapvar_pack's arrays: the CPU twin of Context.hapvar_windows."""
+    out = C.POINTER(gq_hapvar_block)()
+    _check(lib().gq_hapvar_host(C.byref(hapvar_input(packed)), int(threads), C.byref(out)))
+    return _hapvar_block(out)
+
+
 def _ptr(a) -> int:
     if isinstance(a, np.ndarray):
         return a.ctypes.data if a.size else 0
@@ -997,6 +1096,13 @@ class Context:
         _check(lib().gq_haplik_windows(self.h, reads.h, dref.h, len(c), c.ctypes.data, s.ctypes.data, e.ctypes.data,
                                        C.byref(ap), C.byref(pb), C.byref(p), C.byref(out)))
         return _haplik_block(out)
+
+    def hapvar_windows(self, packed: Dict[str, np.ndarray]) -> Dict[str, object]:
+        """gq_hapvar_windows over hapvar_pack's arrays: the windows' events, their carriers and genotype
+        likelihoods, the haplotype and window flags and the call's spans."""
+        out = C.POINTER(gq_hapvar_block)()
+        _check(lib().gq_hapvar_windows(self.h, C.byref(hapvar_input(packed)), C.byref(out)))
+        return _hapvar_block(out)
 
     def align_reads(self, reads: "DeviceReads", dref: "DeviceReference", pad: int = 32, all_reads: bool = False,
                     **probabilities) -> Dict[str, object]:

@@ -1114,6 +1114,106 @@ gq_status gq_haplik_genotypes_host(int64_t n_windows, const int64_t *win_read_of
                                    const int64_t *lik_off, const double *scaled, int64_t *gt_off,
                                    double *gt_log_likelihood, int64_t gt_capacity, int32_t *best_genotype);
 
+/* Variants from assembled haplotypes: the events the aligned haplotypes of a window carry, and per
+ * event the likelihoods of the genotypes 0/0, 0/1, 1/1 marginalised over the haplotypes (DESIGN.md
+ * "Variants from haplotypes").  This contract is the project's own; the reference has no such stage.
+ * Inputs (gq_hapvar_input, host arrays; the device entry uploads them): per window w its contig
+ * coordinate win_start[w] and its win_len[w] reference bytes at ref_pool + ref_off[w] (ref_off[w] < 0:
+ * none); hap_off, hap_seq_off, bases of a path block; per haplotype hap_align[h], an index into the
+ * alignment arrays (ref_start, ref_end, cigar_off, cigar of a gq_alignments over n_align pairs) or -1
+ * when the haplotype was not aligned; win_read_off, lik_off, scaled of a likelihood block.
+ * Usable haplotypes.  Haplotype h of window w is usable iff hap_align[h] >= 0, the window has reference
+ * bytes, ref_start == 0 and ref_end == win_len[w].  Otherwise hap_flags[h] is GQ_HV_HAP_UNALIGNED (no
+ * alignment, or no reference bytes) or GQ_HV_HAP_PARTIAL; such a haplotype makes no events and takes no
+ * part in any sum or maximum below.  Haplotypes are indexed within their window; a window with more
+ * than 64 is GQ_E_CAPACITY naming the window (the carrier sets are 64-bit masks), nothing is truncated
+ * and *out is not written.  A usable haplotype's CIGAR must hold only = (7) X (8) I (1) D (2) ops of
+ * length >= 1 that consume exactly win_len window bytes and the haplotype's bytes, else GQ_E_ARG.
+ * Events of a usable haplotype.  Walk its CIGAR from window offset 0 and haplotype offset 0.  X of
+ * length L: L SNV events, one per base, REF the window byte, ALT the haplotype byte.  I of length L at
+ * window offset p: left-normalised first: while the base just before the insertion is a matched (=)
+ * base of this alignment and equals the insertion's last base, the insertion moves one base to the left
+ * (the inserted bytes stay a substring of the haplotype, one to the left); a base under X, I or D stops
+ * the shift.  An insertion then at offset 0 has no anchor: it is dropped, the window gets
+ * GQ_HV_EDGE_DROPPED and n_edge_dropped counts it.  Otherwise the event stands at offset p - 1 with REF
+ * the anchor byte (the window's) and ALT the anchor byte followed by the L inserted bytes.  D of length
+ * L: left-normalised the same way, while the preceding matched base equals the last deleted base; the
+ * same edge rule; the event stands at p - 1 with REF the L + 1 window bytes from the anchor and ALT the
+ * anchor byte.  An event is (window offset, kind, ref_len, alt_len, ALT bytes).
+ * Events of a window: the distinct events over its usable haplotypes, sorted by (window offset,
+ * ref_len, alt_len, ALT bytes as unsigned bytes); carriers[e] has bit h set iff usable haplotype h made
+ * event e; pos[e] = win_start[w] + offset, 0-based.  A window whose raw events (before dedup, dropped
+ * ones not counted) exceed the cap gq_hapvar_limits reports gets GQ_HV_TOO_MANY_EVENTS and no events;
+ * the host twin has no cap but applies the same flag at the same threshold.
+ * Likelihoods of event e of window w with N reads in list order, H haplotypes, usable set U: C =
+ * carriers[e], R = U \ C.  For read n alt[n] = the maximum of scaled[lik_off[w] + n * H + h] over h in C
+ * and ref[n] the same over h in R, 0.0 when R is empty (the event then has GQ_HV_NO_REF_SIDE).  For the
+ * genotypes 0/0, 0/1, 1/1 with (x, y) = (ref, ref), (ref, alt), (alt, alt):  gl = 0; for n ascending:
+ * gl = gl + ((log(x + y) - log(INIT)) - log(2.0)), INIT = 2^1000, fdlibm's log, every operation rounded
+ * on its own (Likelihood.likelihoodsOfGenotypes with a uniform prior, as the window genotypes above).
+ * A read whose two values are both 0 makes the genotype -infinity; N == 0 gives three zeros.  best[e]
+ * is the first largest of the three; ad_ref[e] counts reads with ref > alt, ad_alt[e] reads with alt >
+ * ref, dp[e] = N.  Two events at one position are scored independently: the other ALT's carriers stand
+ * on the REF side.                                                                               */
+enum { GQ_HV_SNV = 0, GQ_HV_INS = 1, GQ_HV_DEL = 2 };
+enum { GQ_HV_HAP_UNALIGNED = 1, GQ_HV_HAP_PARTIAL = 2 };             /* hap_flags */
+enum { GQ_HV_EDGE_DROPPED = 1, GQ_HV_TOO_MANY_EVENTS = 2 };          /* win_flags */
+enum { GQ_HV_NO_REF_SIDE = 1 };                                      /* ev_flags  */
+typedef struct {
+  int64_t n_windows, n_haplotypes, n_align;
+  const int32_t *win_start;      /* [n_windows]                                                  */
+  const uint8_t *ref_pool;
+  const int64_t *ref_off;        /* [n_windows] < 0: the window has no reference bytes           */
+  const int32_t *win_len;        /* [n_windows]                                                  */
+  const int64_t *hap_off;        /* [n_windows + 1]                                              */
+  const int64_t *hap_seq_off;    /* [n_haplotypes + 1] into bases                                */
+  const uint8_t *bases;
+  const int64_t *hap_align;      /* [n_haplotypes] into the four arrays below, or -1             */
+  const int32_t *ref_start, *ref_end;  /* [n_align]                                              */
+  const int64_t *cigar_off;      /* [n_align + 1] into cigar                                     */
+  const uint32_t *cigar;
+  const int64_t *win_read_off;   /* [n_windows + 1]                                              */
+  const int64_t *lik_off;        /* [n_windows + 1]                                              */
+  const double *scaled;
+} gq_hapvar_input;
+typedef struct {
+  int64_t n_windows, n_events, n_haplotypes, n_alt_bases;
+  int64_t *ev_off;               /* [n_windows + 1] a window's events, in the order above        */
+  int64_t *pos;                  /* [n_events] 0-based contig coordinate                         */
+  uint8_t *kind;                 /* [n_events] GQ_HV_SNV / INS / DEL                             */
+  int32_t *ref_len;              /* [n_events] REF = the window's bytes from the event's offset  */
+  int64_t *alt_off;              /* [n_events] into alt_bases                                    */
+  int32_t *alt_len;              /* [n_events]                                                   */
+  uint8_t *alt_bases;            /* [n_alt_bases]                                                */
+  uint64_t *carriers;            /* [n_events]                                                   */
+  double *gl;                    /* [3 * n_events] 0/0, 0/1, 1/1                                 */
+  int32_t *best;                 /* [n_events]                                                   */
+  int32_t *ad_ref, *ad_alt, *dp; /* [n_events]                                                   */
+  uint8_t *ev_flags;             /* [n_events] GQ_HV_NO_REF_SIDE                                 */
+  uint8_t *hap_flags;            /* [n_haplotypes]                                               */
+  uint8_t *win_flags;            /* [n_windows]                                                  */
+  int64_t n_edge_dropped;
+  float ms;                      /* device span of the call, copies included (0: host twin)      */
+  float events_ms;               /* ... of the event kernels, the count read-back included       */
+  float marginal_ms;             /* ... of hv_marginal_k                                         */
+  int32_t reserved;
+  void *block_;                  /* owner of the arrays above (gq_hapvar_free_block)             */
+} gq_hapvar_block;
+#ifdef __cplusplus
+static_assert(sizeof(gq_hapvar_input) == 144, "gq_hapvar_input layout");
+static_assert(sizeof(gq_hapvar_block) == 192, "gq_hapvar_block layout");
+#endif
+/* out[0..7]: haplotypes a window may have (64), the raw-event cap of a window, threads per window of
+ * the sort kernel, bytes of LDS its sort buffer takes, reads per pass of hv_marginal_k, 0, 0, 0    */
+void gq_hapvar_limits(int32_t out[8]);
+/* GQ_E_ARG on a null or negative argument, a window with a negative length or counts, a hap_align
+ * outside [-1, n_align) or a CIGAR that does not fit (above).  n_windows == 0: an empty block.     */
+gq_status gq_hapvar_windows(gq_ctx *ctx, const gq_hapvar_input *in, gq_hapvar_block **out);
+/* The same block on the CPU (plain C++, no device), bit for bit; `threads` workers over the windows
+ * (<= 1: the calling thread).                                                                      */
+gq_status gq_hapvar_host(const gq_hapvar_input *in, int32_t threads, gq_hapvar_block **out);
+void gq_hapvar_free_block(gq_hapvar_block *b);
+
 #ifdef __cplusplus
 }
 #endif
