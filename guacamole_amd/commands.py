@@ -1255,6 +1255,109 @@ def pileup_counts_main(argv: Sequence[str]) -> int:
     return 0
 
 
+ACTIVE_OPTIONS = (("min_mapq", "Minimum read mapping quality for the evidence pileup"),
+                  ("min_depth", "Minimum filtered depth of an active locus"),
+                  ("min_evidence", "Minimum non-reference A/C/G/T, insertion and deletion elements at an active locus"),
+                  ("min_percent", "Minimum share of the depth the evidence must reach, in percent"),
+                  ("pad", "Loci added on each side of an active locus"))
+
+
+def _active_options(p: argparse.ArgumentParser, prefix: str = "") -> None:
+    for name, text in ACTIVE_OPTIONS:
+        p.add_argument("--%s%s" % (prefix, name.replace("_", "-")), type=int, default=native.ACTIVE_DEFAULTS[name],
+                       dest="active_" + name, help=text)
+
+
+def _active_params(args) -> dict:
+    prm = {name: getattr(args, "active_" + name) for name, _ in ACTIVE_OPTIONS}
+    if prm["pad"] < 0:
+        raise ValueError("the active-region pad must not be negative")
+    if not 0 <= prm["min_percent"] <= 100:
+        raise ValueError("the active-region percent must lie in 0..100")
+    return prm
+
+
+def active_regions_main(argv: Sequence[str]) -> int:
+    """active-regions: the regions of the loci where the pileup shows evidence of a variant
+    (gq_active_regions_call), as TSV: contig, start, end, n_active, evidence."""
+    import os
+    from . import active
+    p = argparse.ArgumentParser(prog="active-regions",
+                                description="regions around the loci whose pileup shows non-reference evidence")
+    p.add_argument("--reads", required=True)
+    p.add_argument("--out", required=True, help="Output TSV path of the regions (must not exist)")
+    p.add_argument("--out-loci", default="", help="Also write one TSV row per active locus: contig, locus, depth, evidence")
+    p.add_argument("--loci", default="all", help="Loci to search (e.g. 'all', 'chr1:0-1000,chr2')")
+    p.add_argument("--loci-from-file", default="", help="Path to file giving loci")
+    _active_options(p)
+    p.add_argument("--parallelism", type=int, default=0, help="Num tasks (loci partitions)")
+    p.add_argument("--partition-accuracy", type=int, default=250,
+                   help="Num micro partitions per task in loci partitioning; 0 = uniform")
+    p.add_argument("--recompute-md-tags", action="store_true")
+    p.add_argument("--reference-fasta", default="",
+                   help="Local path to a reference FASTA file: MD tags for reads without one (all reads with "
+                        "--recompute-md-tags)")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    p.add_argument("--chunk-loci", type=int, default=1 << 24,
+                   help="Loci per library call (whole tasks; a larger task goes alone)")
+    args = p.parse_args(argv)
+    single_process_only("active-regions")
+    for path in (args.out, args.out_loci):
+        if path and os.path.lexists(path):
+            raise FileExistsError("Output path %s already exists" % path)
+    if args.chunk_loci < 1:
+        raise ValueError("--chunk-loci must be at least 1")
+    prm = _active_params(args)
+    builder = _loci_builder(args)
+    filters = InputFilters.make(overlaps_loci=builder, mapped=True, non_duplicate=True, has_md_tag=True)
+    ctx, (rs,) = load_product_reads(args, filters, args.reads)
+    loci = builder.result(rs.contig_lengths_map)
+    flat = flatten_partitions(partition(loci, args.parallelism, args.partition_accuracy, rs), rs.contig_index())
+    if ctx is None:
+        ctx = native.Context(args.device)
+    found: list = []
+    info: dict = {}
+    regions = active.find_regions(ctx, device_reads(ctx, rs), flat, chunk_loci=args.chunk_loci, loci_out=found, info=info,
+                                  **prm)
+    names, lengths = list(rs.contig_names), dict(rs.contig_lengths_map)
+    active.write_tsv(args.out, active.named(regions, names), lengths)
+    if args.out_loci:
+        active.write_loci_tsv(args.out_loci, active.named(found, names))
+    print("Wrote %d active regions of %d active loci (%d loci visited)." % (len(regions), len(found), info["visited_loci"]),
+          file=sys.stderr)
+    return 0
+
+
+def active_windows(args, ctx, dr, dref, rs, loci: LociSet, clock: "StageClock", info: dict):
+    """The windows of an assembly command under --active-regions: the regions found over `loci` (one
+    task), cut by active.regions_to_windows in place of the grid.  The evidence pileup needs MD events:
+    reads without them get theirs from the resident reference first (Context.rebuild_md)."""
+    from . import active
+    if ctx.missing_md(dr) > 0:
+        ctx.rebuild_md(dr, dref)
+    names = list(rs.contig_names)
+    flat = flatten_partitions(partition_loci_uniformly(1, loci), rs.contig_index())
+    regions = active.find_regions(ctx, dr, flat, info=info, **_active_params(args))
+    windows = active.regions_to_windows(active.named(regions, names), dict(rs.contig_lengths_map), args.window_size,
+                                        args.window_step or None, args.kmer_size)
+    info["regions"] = len(regions)
+    clock.mark("active_regions")
+    return windows
+
+
+def _active_report(info: dict) -> dict:
+    """What the stage report gains under --active-regions (nothing without it)."""
+    if not info:
+        return {}
+    return dict(regions=info["regions"], active_loci=info["active_loci"], active_ms=info["total_ms"],
+                active_staging_ms=info["staging_ms"], active_regions_ms=info["regions_ms"])
+
+
+def _active_summary(info: dict) -> str:
+    """What the summary line gains under --active-regions (nothing without it)."""
+    return " The windows cover %d active regions of %d active loci." % (info["regions"], info["active_loci"]) if info else ""
+
+
 def warn_default_parallelism(args, world: int) -> None:
     """--parallelism 0 means one task per rank (task_count): the records at heap-order loci then
     depend on the rank count, so say so when a multi-rank run takes the default."""
@@ -1392,6 +1495,9 @@ def assemble_windows_main(argv: Sequence[str]) -> int:
     p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
     p.add_argument("--max-paths", type=int, default=10)
     p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--active-regions", action="store_true",
+                   help="Assemble only the active regions found over --loci (the --active-* thresholds), not its grid")
+    _active_options(p, "active-")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     args = p.parse_args(argv)
     single_process_only("assemble-windows")
@@ -1410,8 +1516,12 @@ def assemble_windows_main(argv: Sequence[str]) -> int:
     dref = ctx.upload_reference(contigs)
     clock.mark("load_reference")
     loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
-    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
-                                   args.window_step or None, args.kmer_size)
+    active_info: dict = {}
+    if args.active_regions:
+        windows = active_windows(args, ctx, dr, dref, rs, loci, clock, active_info)
+    else:
+        windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                       args.window_step or None, args.kmer_size)
     info: dict = {}
     try:
         rows = assemble.assemble_windows(ctx, dr, dref, windows, names, dict(zip(names, contigs)), k=args.kmer_size,
@@ -1424,10 +1534,10 @@ def assemble_windows_main(argv: Sequence[str]) -> int:
         fh.write(assemble.TSV_HEADER + "\n")
         fh.writelines(l + "\n" for l in assemble.tsv_lines(rows))
     clock.mark("write")
-    print("Assembled %d windows into %d haplotypes; wrote %d rows." % (len(windows), info["n_haplotypes"], len(rows)),
-          file=sys.stderr)
+    print("Assembled %d windows into %d haplotypes; wrote %d rows.%s" %
+          (len(windows), info["n_haplotypes"], len(rows), _active_summary(active_info)), file=sys.stderr)
     clock.report(windows=len(windows), graphs_ms=info["ms"], paths_ms=info["paths_ms"], align_ms=info["align_ms"],
-                 global_windows=info["n_global"])
+                 global_windows=info["n_global"], **_active_report(active_info))
     return 0
 
 
@@ -1451,6 +1561,9 @@ def haplotype_likelihoods_main(argv: Sequence[str]) -> int:
     p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
     p.add_argument("--max-paths", type=int, default=10)
     p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--active-regions", action="store_true",
+                   help="Assemble only the active regions found over --loci (the --active-* thresholds), not its grid")
+    _active_options(p, "active-")
     p.add_argument("--quality-floor", type=int, default=None, help="Base qualities below it count as it (6)")
     p.add_argument("--mismatch-probability", type=float, default=None, help="For reads without qualities")
     p.add_argument("--open-gap-probability", type=float, default=None)
@@ -1474,8 +1587,12 @@ def haplotype_likelihoods_main(argv: Sequence[str]) -> int:
     dref = ctx.upload_reference(contigs)
     clock.mark("load_reference")
     loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
-    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
-                                   args.window_step or None, args.kmer_size)
+    active_info: dict = {}
+    if args.active_regions:
+        windows = active_windows(args, ctx, dr, dref, rs, loci, clock, active_info)
+    else:
+        windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                       args.window_step or None, args.kmer_size)
     info: dict = {}
     try:
         graphs, paths = assemble.graphs_and_paths(ctx, dr, dref, windows, names, k=args.kmer_size,
@@ -1497,10 +1614,11 @@ def haplotype_likelihoods_main(argv: Sequence[str]) -> int:
             fh.write(haplotypes.READ_HEADER + "\n")
             fh.writelines(l + "\n" for l in haplotypes.read_tsv_lines(reads))
     clock.mark("write")
-    print("%d windows, %d read-haplotype pairs (%d underflowed), %d genotypes; wrote %d rows." %
-          (len(windows), info["n_pairs"], info["n_underflow"], info["n_genotypes"], len(rows)), file=sys.stderr)
+    print("%d windows, %d read-haplotype pairs (%d underflowed), %d genotypes; wrote %d rows.%s" %
+          (len(windows), info["n_pairs"], info["n_underflow"], info["n_genotypes"], len(rows),
+           _active_summary(active_info)), file=sys.stderr)
     clock.report(windows=len(windows), graphs_ms=graphs.info["ms"], paths_ms=paths["ms"], haplik_ms=info["haplik_ms"],
-                 kernel_ms=info["haplik_kernel_ms"], genotype_ms=info["genotype_ms"])
+                 kernel_ms=info["haplik_kernel_ms"], genotype_ms=info["genotype_ms"], **_active_report(active_info))
     return 0
 
 
@@ -1526,6 +1644,9 @@ def germline_assembly_main(argv: Sequence[str]) -> int:
     p.add_argument("--window-step", type=int, default=0, help="Distance between window starts (default: the size)")
     p.add_argument("--max-paths", type=int, default=10)
     p.add_argument("--min-mapq", type=int, default=1, help="Only reads of at least this mapping quality")
+    p.add_argument("--active-regions", action="store_true",
+                   help="Assemble only the active regions found over --loci (the --active-* thresholds), not its grid")
+    _active_options(p, "active-")
     p.add_argument("--quality-floor", type=int, default=None, help="Base qualities below it count as it (6)")
     p.add_argument("--mismatch-probability", type=float, default=None, help="For reads without qualities")
     p.add_argument("--open-gap-probability", type=float, default=None)
@@ -1549,8 +1670,12 @@ def germline_assembly_main(argv: Sequence[str]) -> int:
     dref = ctx.upload_reference(contigs)
     clock.mark("load_reference")
     loci = LociSet.parse(args.loci).result(rs.contig_lengths_map)
-    windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
-                                   args.window_step or None, args.kmer_size)
+    active_info: dict = {}
+    if args.active_regions:
+        windows = active_windows(args, ctx, dr, dref, rs, loci, clock, active_info)
+    else:
+        windows = assemble.cut_windows([r for r in loci.ranges() if r[0] in set(names)], args.window_size,
+                                       args.window_step or None, args.kmer_size)
     info: dict = {}
     try:
         rows, _, _ = variants_assembly.call_windows(
@@ -1570,12 +1695,12 @@ def germline_assembly_main(argv: Sequence[str]) -> int:
             fh.writelines(l + "\n" for l in variants_assembly.event_tsv_lines(rows))
     clock.mark("write")
     print("%d windows, %d haplotypes (%d not usable), %d events (%d indels dropped at a window's edge, %d windows "
-          "over the event cap); wrote %d calls." %
+          "over the event cap); wrote %d calls.%s" %
           (len(windows), info["n_haplotypes"], info["n_unusable"], info["n_events"], info["n_edge_dropped"],
-           info["n_capped_windows"], len(calls)), file=sys.stderr)
+           info["n_capped_windows"], len(calls), _active_summary(active_info)), file=sys.stderr)
     clock.report(windows=len(windows), graphs_ms=info["graphs_ms"], paths_ms=info["paths_ms"], align_ms=info["align_ms"],
                  haplik_ms=info["haplik_ms"], hapvar_ms=info["hapvar_ms"], events_ms=info["events_ms"],
-                 marginal_ms=info["marginal_ms"])
+                 marginal_ms=info["marginal_ms"], **_active_report(active_info))
     return 0
 
 
@@ -1583,7 +1708,7 @@ COMMANDS = {"germline-threshold": germline_threshold_main, "somatic-standard": s
             "variant-support": variant_support_main, "vaf-histogram": vaf_histogram_main,
             "germline-standard": germline_standard_main, "allele-evidence": allele_evidence_main,
             "genotype-likelihoods": genotype_likelihoods_main, "pileup-elements": pileup_elements_main, "somatic-likelihoods": somatic_likelihoods_main,
-            "pileup-counts": pileup_counts_main, "structural-variant": structural_variant_main,
+            "pileup-counts": pileup_counts_main, "active-regions": active_regions_main, "structural-variant": structural_variant_main,
             "realign-reads": realign_reads_main, "assemble-windows": assemble_windows_main,
             "haplotype-likelihoods": haplotype_likelihoods_main, "germline-assembly": germline_assembly_main}
 

@@ -40,6 +40,7 @@
 #include "gq_host.h"
 #include "gq_strictmath.h"
 #include "gq_scala_order.h"
+#include "gq_active_host.h"
 
 // The caller's FP64 arithmetic must round like the reference's: no fused multiply-add
 // anywhere in this file (e.g. (agg + 0) - ln2 * depth would otherwise contract).
@@ -1265,6 +1266,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DEEP ? 1
 #include "gq_genotype_likelihoods.h"
 #include "gq_pileup_elements.h"
 #include "gq_pileup_counts.h"
+#include "gq_active.h"
 #include "gq_somatic_likelihoods.h"
 
 gq_status ensure_margin_projection(gq_ctx *c, const gq_dev_reads *t, int min_mapq, bool incl_align = true) {
@@ -2775,13 +2777,25 @@ PcLayout pc_layout(int64_t n_rows) {
   L.bytes = al(L.kind_count + 16 * N + 1);
   return L;
 }
-// The call into `res` (zeroed; the caller frees it, block included, when this fails).
-gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_pileup_counts_params *p,
-                            gq_pileup_count_rows *res) {
-  const auto h0 = std::chrono::steady_clock::now();
+// The finished staging of a call: a row and a keep word per locus of the tiles a read overlaps
+// (tiles in call order), in the context's buffers until its next call.  n_loci == 0: nothing was
+// staged (no tile, or no read over any).
+struct PcStaging {
+  Plan pl;
+  int64_t n_loci = 0;  // staging rows
+  PcRow *rows = nullptr;
+  uint32_t *keep = nullptr, *inc = nullptr;  // inc: room for the keep words' scan
+  Counters hc{};                             // the counters as last read (err: a kernel raised an error)
+  Counters *ctr = nullptr;
+  int64_t n_items = 0;  // loci handed to the per-locus kernel
+};
+// Everything up to the finished staging rows (the tile kernel, the listed-locus kernel, the
+// heap-order replay), shared by pileup-counts and active-regions.  Records ev[0] .. ev[3].
+gq_status pileup_counts_stage(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_pileup_counts_params *p,
+                              PcStaging &S) {
   c->timings = gq_timings{};
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  Plan pl;
+  Plan &pl = S.pl;
   gq_status st = ensure_columns(c, rd);  // (the walker's clean fast path)
   if (st) return st;
   st = plan(c, rd, loci, kPcT, pl, c->tiles);
@@ -2834,9 +2848,9 @@ gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *lo
   uint32_t *keep = (uint32_t *)c->keys.p, *inc = (uint32_t *)c->keys_sorted.p;
   unsigned long long item_cap = (unsigned long long)std::min<int64_t>(n_loci, std::max<int64_t>(n_loci / 8, 1 << 16)),
                      amb_cap = 4096;
-  Counters hc{};
-  Counters *ctr = nullptr;
-  int64_t n_items = 0;
+  Counters &hc = S.hc;
+  Counters *&ctr = S.ctr;
+  int64_t &n_items = S.n_items;
   for (;;) {
     HIP_TRY(c->amb.ensure(amb_cap * sizeof(AmbItem)));
     HIP_TRY(c->cplx.ensure(item_cap * sizeof(ComplexItem)));
@@ -2890,6 +2904,26 @@ gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *lo
     }
     break;
   }
+  S.n_loci = n_loci;
+  S.rows = rows;
+  S.keep = keep;
+  S.inc = inc;
+  return GQ_OK;
+}
+// The call into `res` (zeroed; the caller frees it, block included, when this fails).
+gq_status pileup_counts_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_pileup_counts_params *p,
+                            gq_pileup_count_rows *res) {
+  const auto h0 = std::chrono::steady_clock::now();
+  PcStaging S;
+  gq_status st = pileup_counts_stage(c, rd, loci, p, S);
+  if (st) return st;
+  if (S.n_loci == 0) return GQ_OK;  // no tile, or no read overlaps the loci
+  const Plan &pl = S.pl;
+  const int64_t n_loci = S.n_loci, n_items = S.n_items;
+  PcRow *rows = S.rows;
+  uint32_t *keep = S.keep, *inc = S.inc;
+  Counters &hc = S.hc;
+  Counters *ctr = S.ctr;
   // ---- the keep words scanned to positions; the total sizes the result block
   size_t tmp = 0;
   HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, keep, inc, (int)n_loci, c->stream));
@@ -2963,6 +2997,153 @@ void gq_free_pileup_counts(gq_pileup_count_rows *r) {
   free(r->block_);  // one block holds every array
   free(r);
 }
+
+namespace {
+// The result until it is handed out; on an early return the stream is drained first, since the copy
+// into the block may still be queued.
+struct ActiveGuard {
+  gq_active_regions *p = nullptr;
+  hipStream_t stream = nullptr;
+  ~ActiveGuard() {
+    if (p && stream) (void)hipStreamSynchronize(stream);
+    gq_active::free_block(p);
+  }
+};
+// Do the call's ranges ascend by (contig, start) without overlap?  The staging rows (tiles in call
+// order) then ascend by key, and so does the compacted list: no sort.
+bool ranges_ascend(const Plan &pl) {
+  for (size_t r = 1; r < pl.rc.size(); ++r)
+    if (pl.rc[r] < pl.rc[r - 1] || (pl.rc[r] == pl.rc[r - 1] && pl.rs[r] < pl.re[r - 1])) return false;
+  return true;
+}
+gq_status active_regions_run(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_active_params *p,
+                             gq_active_regions **out) {
+  const auto h0 = std::chrono::steady_clock::now();
+  // the staging keeps what can be active: depth >= min_depth and depth > ref_depth (e >= 1 needs it)
+  const gq_pileup_counts_params cp{p->min_mapq, p->min_depth, 1, 0};
+  PcStaging S;
+  gq_status st = pileup_counts_stage(c, rd, loci, &cp, S);
+  if (st) return st;
+  ActiveGuard res;
+  auto hand_out = [&]() {
+    *out = res.p;
+    res.p = nullptr;
+    return GQ_OK;
+  };
+  if (S.n_loci == 0) {  // no tile, or no read overlaps the loci
+    res.p = gq_active::new_block(0, 0);
+    if (!res.p) return set_err(GQ_E_NOMEM, "active-regions result block");
+    return hand_out();
+  }
+  const int64_t n_loci = S.n_loci;
+  Counters &hc = S.hc;
+  // ---- the predicate into the keep words, their scan, the number of active loci
+  size_t tmp = 0;
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, S.keep, S.inc, (int)n_loci, c->stream));
+  HIP_TRY(c->sort_tmp.ensure(tmp));
+  uint32_t n_act32 = 0;
+  if (!hc.err) {
+    hipLaunchKernelGGL(active_mark, dim3((unsigned)((n_loci + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       (const PcRow *)S.rows, S.keep, n_loci, *p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->sort_tmp.p, tmp, S.keep, S.inc, (int)n_loci, c->stream));
+    HIP_TRY(hipMemcpyAsync(&n_act32, S.inc + (n_loci - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(&hc, S.ctr, kCountersHead, hipMemcpyDeviceToHost, c->stream));  // (the second pass' errors)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < kSpread; ++k) hc.visited += hc.spread[0][k];
+  st = check_device_error(c, hc);
+  if (st) return st;
+  const int64_t n_act = (int64_t)n_act32;
+  int64_t n_regions = 0;
+  gq_active::Layout lay = gq_active::layout(0, 0);
+  if (n_act > 0) {
+    // the active list: (key, depth | e) pairs, twice for the sort; heads and their scan; the flag
+    const size_t N = (size_t)n_act;
+    HIP_TRY(c->recs_sorted.ensure(4 * 8 * N));
+    HIP_TRY(c->idx.ensure(4 * N + 4));
+    HIP_TRY(c->idx_sorted.ensure(4 * N));
+    uint64_t *key = (uint64_t *)c->recs_sorted.p, *val = key + N, *key2 = val + N, *val2 = key2 + N;
+    uint32_t *head = (uint32_t *)c->idx.p, *disorder = head + N, *hinc = (uint32_t *)c->idx_sorted.p;
+    const unsigned blocks = (unsigned)((n_act + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(active_compact, dim3((unsigned)((n_loci + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       (const PcRow *)S.rows, (const uint32_t *)S.keep, (const uint32_t *)S.inc, n_loci, n_act, key, val);
+    HIP_TRY(hipGetLastError());
+    if (!ranges_ascend(S.pl)) {  // every bit of the key: the contig's above the position's
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, key, key2, val, val2, (int)n_act, 0, 64, c->stream));
+      HIP_TRY(c->sort_tmp.ensure(tmp));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->sort_tmp.p, tmp, key, key2, val, val2, (int)n_act, 0, 64, c->stream));
+      std::swap(key, key2);
+      std::swap(val, val2);
+    }
+    HIP_TRY(hipMemsetAsync(disorder, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(active_heads, dim3(blocks), dim3(kBlock), 0, c->stream, (const uint64_t *)key, n_act, p->pad, head,
+                       disorder);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, head, hinc, (int)n_act, c->stream));
+    HIP_TRY(c->sort_tmp.ensure(tmp));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->sort_tmp.p, tmp, head, hinc, (int)n_act, c->stream));
+    uint32_t back[2] = {0, 0};  // regions; keys that descend (the list was taken for sorted and is not)
+    HIP_TRY(hipMemcpyAsync(&back[0], hinc + (n_act - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&back[1], disorder, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (back[1]) return set_err(GQ_E_ASSERT, "active-regions: the active loci do not ascend");
+    n_regions = (int64_t)back[0];
+    lay = gq_active::layout(n_regions, n_act);
+    HIP_TRY(c->image.ensure(lay.bytes));
+    hipLaunchKernelGGL(active_write, dim3(blocks), dim3(kBlock), 0, c->stream, (const uint64_t *)key, (const uint64_t *)val,
+                       (const uint32_t *)head, (const uint32_t *)hinc, n_act, n_regions, p->pad, lay, (uint8_t *)c->image.p);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+  res.p = gq_active::new_block(n_regions, n_act);
+  if (!res.p) return set_err(GQ_E_NOMEM, "active-regions result block of %zu bytes", lay.bytes);
+  res.stream = c->stream;
+  if (n_act > 0) HIP_TRY(hipMemcpyAsync(res.p->block_, c->image.p, lay.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  res.p->visited_loci = (int64_t)hc.visited;
+  res.p->listed_loci = S.n_items;
+  fill_timings(c, h0, S.pl.n_tiles, nullptr, 5);
+  return hand_out();
+}
+}  // namespace
+
+// timings: pileup_ms the tile kernel, complex_ms the per-locus kernel (heap-order round trip
+// included), finalize_ms the kernels after the staging (predicate, compaction, sort, heads, regions)
+// with their two count read-backs, walk_ms the device-to-host copy of the block.
+gq_status gq_active_regions_call(gq_ctx *c, const gq_dev_reads *rd, const gq_loci *loci, const gq_active_params *p,
+                                 gq_active_regions **out) {
+  if (!c || !rd || !loci || !p || !out) return set_err(GQ_E_ARG, "gq_active_regions_call: null argument");
+  if (!gq_active::params_ok(p))
+    return set_err(GQ_E_ARG, "gq_active_regions_call: pad %d, min_percent %d", p->pad, p->min_percent);
+  HIP_TRY(hipSetDevice(c->device));
+  {  // (a re-derivation still queued on the stream: its validation first)
+    const gq_status vs = gq::validation_wait(rd);
+    if (vs) return vs;
+  }
+  return active_regions_run(c, rd, loci, p, out);
+}
+
+gq_status gq_active_regions_host(int64_t n_rows, const int32_t *contig, const int64_t *pos, const uint8_t *ref_base,
+                                 const int32_t *depth, const int32_t *ref_depth, const int32_t *base_count,
+                                 const int32_t *kind_count, const gq_active_params *p, gq_active_regions **out) {
+  if (!p || !out || n_rows < 0 ||
+      (n_rows > 0 && (!contig || !pos || !ref_base || !depth || !ref_depth || !base_count || !kind_count)))
+    return set_err(GQ_E_ARG, "gq_active_regions_host: null or negative argument");
+  if (!gq_active::params_ok(p))
+    return set_err(GQ_E_ARG, "gq_active_regions_host: pad %d, min_percent %d", p->pad, p->min_percent);
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (contig[i] < 0 || pos[i] < 0 || pos[i] > (int64_t)INT32_MAX)
+      return set_err(GQ_E_ARG, "gq_active_regions_host: row %lld at contig %d, position %lld", (long long)i, contig[i],
+                     (long long)pos[i]);
+  gq_active_regions *r = gq_active::run_host(n_rows, contig, pos, ref_base, depth, ref_depth, base_count, kind_count, *p);
+  if (!r) return set_err(GQ_E_NOMEM, "gq_active_regions_host: result block");
+  *out = r;
+  return GQ_OK;
+}
+
+void gq_free_active_regions(gq_active_regions *r) { gq_active::free_block(r); }
 
 namespace {
 SlLayout sl_layout(int64_t n_groups, const int64_t (&n_alleles)[2], const int64_t (&n_geno)[2], int64_t dev_pool_used) {

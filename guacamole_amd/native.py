@@ -239,6 +239,20 @@ class gq_pileup_count_rows(C.Structure):
                 ("block_bytes", C.c_int64), ("block_", C.c_void_p)]
 
 
+class gq_active_params(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("min_depth", C.c_int32), ("min_evidence", C.c_int32),
+                ("min_percent", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class gq_active_regions(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int64)),
+                ("end", C.POINTER(C.c_int64)), ("n_active", C.POINTER(C.c_int32)), ("evidence", C.POINTER(C.c_int64)),
+                ("n_loci", C.c_int64), ("locus_contig", C.POINTER(C.c_int32)), ("locus_pos", C.POINTER(C.c_int64)),
+                ("locus_depth", C.POINTER(C.c_int32)), ("locus_evidence", C.POINTER(C.c_int32)),
+                ("visited_loci", C.c_int64), ("listed_loci", C.c_int64), ("block_bytes", C.c_int64),
+                ("block_", C.c_void_p)]
+
+
 class gq_md_rebuild_info(C.Structure):
     _fields_ = [("read", C.c_int64), ("code", C.c_int32), ("pad", C.c_int32), ("rebuilt", C.c_int64),
                 ("md_events", C.c_int64), ("ms", C.c_float)]
@@ -368,7 +382,8 @@ EXPORTED = ("gq_version", "gq_last_error", "gq_open", "gq_close", "gq_get_timing
             "gq_asm_paths", "gq_asm_free_paths",
             "gq_haplik_default_params", "gq_haplik_tables", "gq_haplik_batch", "gq_haplik_host", "gq_haplik_free_pairs",
             "gq_haplik_windows", "gq_haplik_free_block", "gq_haplik_genotypes_host",
-            "gq_hapvar_limits", "gq_hapvar_windows", "gq_hapvar_host", "gq_hapvar_free_block")
+            "gq_hapvar_limits", "gq_hapvar_windows", "gq_hapvar_host", "gq_hapvar_free_block",
+            "gq_active_regions_call", "gq_active_regions_host", "gq_free_active_regions")
 
 
 def lib():
@@ -430,6 +445,14 @@ def lib():
                                             C.POINTER(C.POINTER(gq_pileup_count_rows))]
         L.gq_free_pileup_counts.argtypes = [C.POINTER(gq_pileup_count_rows)]
         L.gq_free_pileup_counts.restype = None
+        L.gq_active_regions_call.restype = C.c_int
+        L.gq_active_regions_call.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_active_params),
+                                             C.POINTER(C.POINTER(gq_active_regions))]
+        L.gq_active_regions_host.restype = C.c_int
+        L.gq_active_regions_host.argtypes = [C.c_int64] + [C.c_void_p] * 7 + [C.POINTER(gq_active_params),
+                                                                              C.POINTER(C.POINTER(gq_active_regions))]
+        L.gq_free_active_regions.argtypes = [C.POINTER(gq_active_regions)]
+        L.gq_free_active_regions.restype = None
         L.gq_vaf_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gq_loci), C.POINTER(gq_vaf_params),
                                        C.POINTER(gq_vaf_hist)]
         L.gq_free_calls.argtypes = [C.POINTER(gq_calls)]
@@ -939,6 +962,72 @@ def hapvar_host(packed: Dict[str, np.ndarray], threads: int = 1) -> Dict[str, ob
     return _hapvar_block(out)
 
 
+ACTIVE_DEFAULTS = dict(min_mapq=1, min_depth=4, min_evidence=2, min_percent=8, pad=75)
+
+
+def active_params(**params) -> gq_active_params:
+    """gq_active_params from keywords (ACTIVE_DEFAULTS where one is missing or None)."""
+    unknown = set(params) - set(ACTIVE_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown active-regions parameters: %s" % ", ".join(sorted(unknown)))
+    v = {k: d if params.get(k) is None else int(params[k]) for k, d in ACTIVE_DEFAULTS.items()}
+    return gq_active_params(v["min_mapq"], v["min_depth"], v["min_evidence"], v["min_percent"], v["pad"])
+
+
+class ActiveRegions:
+    """A gq_active_regions block as numpy columns copied out of it: the regions (``contig``, ``start``,
+    ``end``, ``n_active``, ``evidence``) ascending by (contig, start), and the active loci in sorted order
+    (``locus_contig``, ``locus_pos``, ``locus_depth``, ``locus_evidence``).  ``contig`` indexes the read
+    set's contigs; ``end`` is not clipped to the contig's length."""
+
+    REGION_COLUMNS = ("contig", "start", "end", "n_active", "evidence")
+    LOCUS_COLUMNS = ("locus_contig", "locus_pos", "locus_depth", "locus_evidence")
+
+    def __init__(self, cols: Dict[str, np.ndarray], visited: int = 0, listed: int = 0, block_bytes: int = 0):
+        self.cols, self.visited_loci, self.listed_loci, self.block_bytes = cols, visited, listed, block_bytes
+
+    @staticmethod
+    def from_struct(c: gq_active_regions) -> "ActiveRegions":
+        def col(name: str, n: int) -> np.ndarray:
+            p = getattr(c, name)
+            return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, p._type_)
+        cols = {k: col(k, int(c.n)) for k in ActiveRegions.REGION_COLUMNS}
+        cols.update({k: col(k, int(c.n_loci)) for k in ActiveRegions.LOCUS_COLUMNS})
+        return ActiveRegions(cols, int(c.visited_loci), int(c.listed_loci), int(c.block_bytes))
+
+    def __len__(self) -> int:
+        return int(self.cols["start"].shape[0])
+
+    @property
+    def regions(self) -> List[tuple]:
+        """(contig index, start, end, n_active, evidence) per region."""
+        return list(zip(*[self.cols[k].tolist() for k in self.REGION_COLUMNS]))
+
+    @property
+    def loci(self) -> List[tuple]:
+        """(contig index, pos, depth, evidence) per active locus."""
+        return list(zip(*[self.cols[k].tolist() for k in self.LOCUS_COLUMNS]))
+
+
+def active_regions_host(contig, pos, ref_base, depth, ref_depth, base_count, kind_count, **params) -> ActiveRegions:
+    """gq_active_regions_host over pileup-count columns (PileupCounts.cols' names; rows in any order): the
+    CPU twin of Context.active_regions."""
+    a = [np.ascontiguousarray(x, dt) for x, dt in ((contig, np.int32), (pos, np.int64), (ref_base, np.uint8),
+                                                   (depth, np.int32), (ref_depth, np.int32),
+                                                   (np.asarray(base_count, np.int32).reshape(-1, 6), np.int32),
+                                                   (np.asarray(kind_count, np.int32).reshape(-1, 4), np.int32))]
+    n = len(a[0])
+    if any(len(x) != n for x in a):
+        raise ValueError("active_regions_host: columns of different lengths")
+    prm = active_params(**params)
+    out = C.POINTER(gq_active_regions)()
+    _check(lib().gq_active_regions_host(n, *[x.ctypes.data if n else None for x in a], C.byref(prm), C.byref(out)))
+    try:
+        return ActiveRegions.from_struct(out.contents)
+    finally:
+        lib().gq_free_active_regions(out)
+
+
 def _ptr(a) -> int:
     if isinstance(a, np.ndarray):
         return a.ctypes.data if a.size else 0
@@ -1287,6 +1376,18 @@ class Context:
             return PileupCounts.from_struct(out.contents)
         finally:
             lib().gq_free_pileup_counts(out)
+
+    def active_regions(self, reads: "DeviceReads", loci, **params) -> "ActiveRegions":
+        """gq_active_regions_call: the regions of `loci` where the pileup shows evidence of a variant
+        (gqpileup.h "active-regions").  params: active_params'."""
+        L, _keep = make_gq_loci(*loci)
+        prm = active_params(**params)
+        out = C.POINTER(gq_active_regions)()
+        _check(lib().gq_active_regions_call(self.h, reads.h, C.byref(L), C.byref(prm), C.byref(out)))
+        try:
+            return ActiveRegions.from_struct(out.contents)
+        finally:
+            lib().gq_free_active_regions(out)
 
     def vaf_histogram(self, reads: "DeviceReads", loci, bins: int = 20, min_read_depth: int = 0,
                       min_vaf: int = 0) -> Dict[str, object]:

@@ -747,6 +747,59 @@ gq_status gq_pileup_counts_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq
                                 const gq_pileup_counts_params *params, gq_pileup_count_rows **out);
 void gq_free_pileup_counts(gq_pileup_count_rows *res);
 
+/* active-regions: the intervals of `loci` where the pileup shows evidence of a variant, found on the
+ * device from the staging rows of pileup-counts (the table never leaves the GPU).  This contract is
+ * the project's own; the reference has no such stage.  All arithmetic is integer.
+ * Evidence.  At a locus take the pileup-counts row of the min_mapq-filtered pileup (reference base:
+ * the unfiltered pileup's, as there).  If ref_base is not one of A C G T, e = 0.  Otherwise
+ *   e = base_count[A] + base_count[C] + base_count[G] + base_count[T] - ref_depth
+ *       + kind_count[Insertion] + kind_count[Deletion] + kind_count[MidDeletion].
+ * Sequenced N, "other" bases and Clipped elements are not evidence.  The locus is active iff
+ *   depth >= max(1, min_depth)  and  e >= max(1, min_evidence)  and  100 * e >= min_percent * depth
+ * (the products in int64).
+ * Regions.  The active loci of the whole call sorted by (contig, pos), whatever the task partition
+ * of `loci`.  Consecutive active loci fall in one region iff they share a contig and
+ * pos - prev <= 2 * pad + 1 (their intervals dilated by pad overlap or touch).  A region is
+ * [max(0, first - pad), last + pad + 1) with n_active, the number of its active loci, and evidence,
+ * the int64 sum of their e.  The upper end is not clipped: the library does not know the contig
+ * lengths here.
+ * Result: one block (block_), filled by one device-to-host copy: the regions, and the active loci
+ * in sorted order (few, and they make a wrong region diagnosable).  No active locus: n == 0 and
+ * n_loci == 0 with a valid block.  GQ_E_ARG: a null pointer, pad < 0, min_percent
+ * outside 0..100.  Capacity limits are gq_pileup_counts_call's.  The host twin takes pileup-count
+ * columns (rows in any order; visited_loci and listed_loci are 0 in its block).                  */
+typedef struct {
+  int32_t min_mapq;      /* 1: as pileup-counts                                         */
+  int32_t min_depth;     /* 4: minimum filtered depth; below 1 counts as 1              */
+  int32_t min_evidence;  /* 2: minimum e; below 1 counts as 1                           */
+  int32_t min_percent;   /* 8: minimum share of the depth e must reach, 0..100          */
+  int32_t pad;           /* 75: dilation on each side of an active locus, >= 0          */
+  int32_t reserved[3];   /* 0                                                           */
+} gq_active_params;
+typedef struct {
+  int64_t n;                   /* regions, ascending by (contig, start)                    */
+  int32_t *contig; int64_t *start; int64_t *end;
+  int32_t *n_active;           /* active loci of the region                                */
+  int64_t *evidence;           /* sum of their e                                           */
+  int64_t n_loci;              /* active loci, ascending by (contig, pos)                  */
+  int32_t *locus_contig; int64_t *locus_pos;
+  int32_t *locus_depth; int32_t *locus_evidence;
+  int64_t visited_loci;        /* loci whose filtered pileup is not empty                  */
+  int64_t listed_loci;         /* loci handed to the per-locus kernel                      */
+  int64_t block_bytes;         /* bytes of block_ (what the device-to-host copy moved)     */
+  void *block_;
+} gq_active_regions;
+#ifdef __cplusplus
+static_assert(sizeof(gq_active_params) == 32, "gq_active_params layout");
+static_assert(sizeof(gq_active_regions) == 120, "gq_active_regions layout");
+#endif
+gq_status gq_active_regions_call(gq_ctx *ctx, const gq_dev_reads *reads, const gq_loci *loci,
+                                 const gq_active_params *params, gq_active_regions **out);
+gq_status gq_active_regions_host(int64_t n_rows, const int32_t *contig, const int64_t *pos, const uint8_t *ref_base,
+                                 const int32_t *depth, const int32_t *ref_depth, const int32_t *base_count,
+                                 const int32_t *kind_count, const gq_active_params *params, gq_active_regions **out);
+void gq_free_active_regions(gq_active_regions *res);
+
 /* structural-variant: large deletions from discordant read pairs (StructuralVariantCaller.scala).
  * No pileup, MD tag or reference is involved; the input need not be sorted.  With len a record's
  * own l_seq, lo / hi the smaller / larger of its start and its mate's start (0-based):
