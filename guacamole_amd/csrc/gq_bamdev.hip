@@ -1076,13 +1076,17 @@ gq_status probe(gq_bam_dev *b, int64_t k, Probe &out) {
     }
   }
   Probe P;
+  bool inflated = false;
   const BgzfBlock &blk = b->blocks[(size_t)k];
   const int64_t o0 = blk.out_off, hi = blk.isize, nb = (int64_t)b->blocks.size();
   const int32_t n_ref = (int32_t)b->names.size();
   if (hi > 0 && o0 + hi > b->rec0) {
-    b->n_probes.fetch_add(1);
+    inflated = true;
     std::vector<uint8_t> buf;
-    if (!host_inflate(b, k, buf)) return corrupt_block(b, k);
+    if (!host_inflate(b, k, buf)) {
+      b->n_probes.fetch_add(1);  // (a failed probe is not cached: counted here, as before)
+      return corrupt_block(b, k);
+    }
     int64_t next = k + 1;
     auto extend = [&](int64_t upto) -> gq_status {  // buf holds >= upto bytes where the stream has them
       while ((int64_t)buf.size() < upto && next < nb && next <= k + 8)
@@ -1128,8 +1132,10 @@ gq_status probe(gq_bam_dev *b, int64_t k, Probe &out) {
     }
   }
   {
+    // (two plan threads may probe one block at once, e.g. the first midpoint of their searches:
+    // the block counts once, so the count is that of the distinct blocks inflated)
     std::lock_guard<std::mutex> g(b->probe_mu);
-    b->probes[k] = P;
+    if (b->probes.emplace(k, P).second && inflated) b->n_probes.fetch_add(1);
   }
   out = P;
   return GQ_OK;

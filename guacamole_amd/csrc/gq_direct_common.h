@@ -8,12 +8,10 @@
 
 // the rotated slot schedule (every group on a slot at the same iteration): somatic_direct's
 // bases and qualities are fetched once instead of ~2.6 times (chr20 60x: FETCH 22.9 -> 8.7 GB,
-// 7.06 -> 6.58 ms); germline_direct, not bound by its fetches, measured 3 % slower with it
+// 7.06 -> 6.58 ms); germline_direct, not bound by its fetches, measured 3 % slower with it and
+// walks its slots in order
 #ifndef GQ_DIR_ROT
 #define GQ_DIR_ROT 1   // somatic_direct
-#endif
-#ifndef GQ_GDIR_ROT
-#define GQ_GDIR_ROT 0  // germline_direct
 #endif
 #ifndef GQ_DIR_GROUP
 #define GQ_DIR_GROUP 4  // lanes (columns) walking their slots together: 1, 2, 4, 8, 16, 32 or 64

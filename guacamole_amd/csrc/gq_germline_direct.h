@@ -24,10 +24,12 @@
 //   counts   lane l walks only the slots that can cover its column: [first slot ending past the
 //            column's first locus, last slot starting before its end] — a prefix maximum and a
 //            suffix minimum of the per-column words.  One unaligned 8-byte buffer load per slot
-//            (three batches of four in flight), the loci outside the run masked, the bases
-//            counted in SWAR registers through v_perm tables (A C T G in nibbles folded into
-//            bytes every 12 slots, N in bytes; the DEEP instantiation widens into 16-bit pairs
-//            every 240).  The same v_perm checks every counted byte is one of A C G T N; a block
+//            (three batches of four in flight), the loci outside the run masked (the half
+//            masks of the column's bytes [a, b) from a table in LDS; a lane past its last
+//            slot reads the empty run behind it), the bases counted in SWAR registers through
+//            v_perm tables (A C T G in nibbles folded into bytes every 12 slots, N in bytes;
+//            the DEEP instantiation widens into 16-bit pairs every 240).  The same v_perm
+//            checks every counted byte is one of A C G T N; a block
 //            with any other byte (an "other" base allele), a read without MD, a CIGAR the
 //            segments cannot express, a round of more than kSlots runs, or more than 65535 window
 //            reads goes to germline_walk, which is exact for every read.
@@ -43,12 +45,6 @@
 
 #ifndef GQ_DIR_WPE
 #define GQ_DIR_WPE 4  // waves per SIMD the register budget must allow
-#endif
-#ifndef GQ_DIR_MASKED
-#define GQ_DIR_MASKED 0
-#endif
-#ifndef GQ_DIR_EVPF
-#define GQ_DIR_EVPF 0
 #endif
 #ifndef GQ_DIR_U
 #define GQ_DIR_U 4
@@ -97,7 +93,10 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
   // the chunk's slots (first locus - B0 | end locus - B0 << 16 as int16s, pool offset of B0's
   // column relative to the tile's base) and per column the last slot starting at or before it /
   // the first slot ending in or after it
-  __shared__ __attribute__((aligned(16))) uint2 rcw[C::kWaves][C::kSlots];
+  // (slot nslot, one past the chunk's last: an empty run, where the lanes past their last slot read)
+  __shared__ __attribute__((aligned(16))) uint2 rcw[C::kWaves][C::kSlots + 1];
+  // the bytes [a, b) of a column's eight as two 32-bit half masks, at [16 a + b] (0 <= a, b <= 8)
+  __shared__ __attribute__((aligned(8))) uint2 mtab[9 * 16];
   __shared__ int32_t hxw[C::kWaves][64], hnw[C::kWaves][64];
   __shared__ unsigned outn[2];
   const int lane = threadIdx.x & 63;
@@ -115,6 +114,11 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
   };
   zero_words();
   if (threadIdx.x < 2) outn[threadIdx.x] = 0;
+  if (threadIdx.x < 9 * 16) {
+    const int32_t b = (int32_t)(threadIdx.x & 15);
+    const uint64_t m = b <= 8 ? byte_range_mask((int32_t)(threadIdx.x >> 4), b) : 0ull;
+    mtab[threadIdx.x] = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+  }
   __syncthreads();
   const int64_t per = n_tiles / gridDim.x, extra = n_tiles % gridDim.x;
   const int64_t i0 = blockIdx.x * per + min((int64_t)blockIdx.x, extra);
@@ -283,10 +287,6 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
     Fields nf = load_fields(rb);
     int64_t c0 = rb;
     bool first_round = true;
-    // GQ_DIR_EVPF: the next round's first four MD events, issued at the end of a round (its
-    // fields have arrived by then), so a round does not start with a dependent load
-    uint32_t pv4[4] = {0u, 0u, 0u, 0u};
-    int64_t pv_c0 = -1;  // the round pv4 belongs to
     while (c0 < re) {  // ---- a chunk: rounds while their runs fit kSlots slots, then the counting
       const uint64_t t_round = (dbg & 16) ? __builtin_readcyclecounter() : 0;
       hx[lane] = -1;
@@ -319,14 +319,7 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
             else atomicAdd(&ev[x], 1u << (8 * cat));
           }
         };
-        if (evr) {
-          if (GQ_DIR_EVPF && pv_c0 == c0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v4[j] = pv4[j];
-          } else {
-            load_ev(0);
-          }
-        }
+        if (evr) load_ev(0);
         // (a general read: slots for its (M|=|X) operations, read_prep's bound on its count
         // segments; those outside the block stay empty)
         if (gen && e > B0 && s < B0 + T) nrun = (uint32_t)min(-1 - ld, C::kSlots);
@@ -436,15 +429,10 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
             load_ev(k0);
           }
         }
-        if (GQ_DIR_EVPF && c0 + C::kRound < re) {  // the next round's first events (nf arrived)
-          const bool nv = c0 + C::kRound + lane < re && nf.nmd > 0 && nf.s < B0 + T;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) pv4[j] = nv ? R.md_ev[nf.mo + (j < nf.nmd ? j : nf.nmd - 1)] : 0u;
-          pv_c0 = c0 + C::kRound;
-        }
         nslot += total;
         c0 += C::kRound;
       }
+      if (lane == 0) rc[nslot] = make_uint2(0u, 0u);  // (nslot <= kSlots) the empty run past the chunk's slots
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const uint64_t t_r = (dbg & 16) ? __builtin_readcyclecounter() : 0;
       // ---- this lane's slots: [first slot ending past its column's first locus, last slot
@@ -457,57 +445,51 @@ __global__ __launch_bounds__(DirCfg::kThreads) __attribute__((amdgpu_waves_per_e
         first = __shfl(first, lane & ~(GQ_DIR_GROUP - 1), 64);
         last = __shfl(last, lane | (GQ_DIR_GROUP - 1), 64);
       }
+      first = min(first, C::kSlots);  // (no slot ends in or after the column: past every slot)
       const int32_t nl = last >= first ? last - first + 1 : 0;
       int32_t kmax = nl;
 #pragma unroll
       for (int d = 1; d < 64; d <<= 1) kmax = max(kmax, __shfl_xor(kmax, d, 64));
       kmax = (dbg & 32) ? 0 : __builtin_amdgcn_readfirstlane(kmax);  // (dbg & 32: no counting)
-      // the slot schedule: iteration k takes the slot s of [first, first + kmax) with s = k (mod
-      // kmax), so every group reaches a slot at the same iteration (k = s mod kmax) and one load
-      // instruction reads a read's bytes for all the groups its run covers (the lines it touches
-      // are fetched once, while they are hot); t0 = the offset of iteration 0
-      const int32_t t0 = (GQ_GDIR_ROT && kmax > 0 && nl > 0) ? (kmax - first % kmax) % kmax : 0;
-      // a batch: U slots' 8-byte loads, all issued before any is used; mt = the column's loci
-      // inside the run [a, b)
+      // a lane past its last slot reads slot last + 1: a run that starts past the group's last
+      // column, an empty (0, 0) slot of a general read, or the empty run at nslot; no locus of
+      // the column lies in any of them (b <= a: mtab's entry is 0) and the lane loads nothing
+      const int32_t lastp1 = last + 1;
+      // a batch: U slots' 8-byte loads, all issued before any is used; mt = 16 a + b, the column's
+      // loci [a, b) inside the run (b <= a: none), the index of their byte masks in mtab
       auto issue = [&](int32_t k0, uint2 (&x)[U], uint32_t (&mt)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int32_t k = k0 + u;
-          int32_t t = t0 + k;  // (GQ_GDIR_ROT) the lane's slot offset at iteration k
-          t = t >= kmax ? t - kmax : t;
-          const bool mine = GQ_GDIR_ROT ? (k < kmax && t < nl) : k < nl;
-          const uint2 d = rc[mine ? first + (GQ_GDIR_ROT ? t : k) : 0];
+          const uint2 d = rc[min(first + k0 + u, lastp1)];
           const int32_t s16 = (int32_t)(int16_t)(d.x & 0xFFFFu), e16 = (int32_t)(int16_t)(d.x >> 16);
           const int32_t a = min(max(s16 - colr, 0), 8), b = min(max(e16 - colr, 0), 8);
-          const bool live = mine && b > a && !(dbg & 1);
+          const bool live = b > a && !(dbg & 1);
           // (vi >= -7 for a live pair, byte a being the run's; < 0 only at the head of a pool with
           // no readable head, whose tiles the DEEP instantiation takes: its load clamped to the
           // base and shifted back)
           const int32_t vi = (int32_t)d.y + colr;
           const uint32_t vo = live ? (uint32_t)(DEEP ? max(vi, 0) : vi) : 0x80000000u;
-          if (GQ_DIR_MASKED) {  // dead lanes off the load (exec-masked) instead of out of range
-            x[u] = make_uint2(0u, 0u);
-            if (live) {
-              const auto w = __builtin_amdgcn_raw_buffer_load_b64(srs, (int)vo, 0, 0);
-              x[u] = make_uint2(w[0], w[1]);
-            }
-          } else {
-            const auto w = __builtin_amdgcn_raw_buffer_load_b64(srs, (int)vo, 0, 0);
-            x[u] = make_uint2(w[0], w[1]);
-          }
-          mt[u] = live ? (uint32_t)a | ((uint32_t)b << 4) | (DEEP ? (uint32_t)max(-vi, 0) << 8 : 0u) : 0u;
+          const auto w = __builtin_amdgcn_raw_buffer_load_b64(srs, (int)vo, 0, 0);
+          x[u] = make_uint2(w[0], w[1]);
+          mt[u] = ((uint32_t)a << 4) | (uint32_t)b | (DEEP ? (uint32_t)max(-vi, 0) << 8 : 0u);
         }
       };
       auto count = [&](const uint2 (&x)[U], const uint32_t (&mt)[U]) {
+        uint2 mm[U];  // the half masks, in flight over the fold
+#pragma unroll
+        for (int u = 0; u < U; ++u) mm[u] = mtab[DEEP ? mt[u] & 0xFFu : mt[u]];
         if (nn + U > 15) fold();
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const uint64_t m = byte_range_mask((int32_t)(mt[u] & 15u), (int32_t)((mt[u] >> 4) & 15u));
-          uint64_t w64 = (uint64_t)x[u].x | ((uint64_t)x[u].y << 32);
-          if (DEEP) w64 <<= (mt[u] >> 5) & 56u;
+          uint32_t w2[2] = {x[u].x, x[u].y};
+          if (DEEP) {
+            const uint64_t w64 = ((uint64_t)x[u].x | ((uint64_t)x[u].y << 32)) << ((mt[u] >> 5) & 56u);
+            w2[0] = (uint32_t)w64;
+            w2[1] = (uint32_t)(w64 >> 32);
+          }
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const uint32_t wh = (uint32_t)(w64 >> (32 * h)), mh = (uint32_t)(m >> (32 * h));
+            const uint32_t wh = w2[h], mh = h ? mm[u].y : mm[u].x;
             const uint32_t xc = wh & 0x07070707u;
             // the byte a code stands for: A 1, C 3, T 4, N 6, G 7 (codes 0 2 5: none)
             const uint32_t ex = __builtin_amdgcn_perm(0x474EFF54u, 0x43FF41FFu, xc);

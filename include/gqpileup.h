@@ -274,7 +274,8 @@ typedef struct {
   int64_t n_blocks;        /* BGZF blocks the load will inflate                                  */
   int64_t comp_bytes;      /* their compressed bytes (the load's host -> device copy)          */
   int64_t bam_bytes;       /* their inflated bytes                                             */
-  int64_t probes;          /* host probes (blocks inflated on the host to read record keys)    */
+  int64_t probes;          /* host probes: distinct blocks inflated on the host to read record
+                            * keys (a block two plan threads reach at once counts once)         */
   int32_t used_index;      /* 1: range starts from the BAI linear index                        */
   int32_t pad;
 } gq_bam_dev_plan_info;
